@@ -133,11 +133,16 @@ def parse_args(argv=None):
                     help="time the drop-in API instead of the kernel pipeline: Trainer.train_iter() -> the three train_ops "
                          "with their .item() host syncs, a fresh uint8 batch per iteration normalised on the device "
                          "(reported under config.api_path; the headline number is the default mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its losses and the trained "
+                         "parameters / BatchNorm buffers, larger tensors as a fixed sample) to DIR/<name>.npy: see dump_outputs")
     ap.add_argument("--step-plugin", default=None,
                     help="TEST HOOK module:function -- replaces the HIP workload by function(args, rank, world, device) -> "
                          "(one_step, flush, items_per_rank_step, info); lets tests/ run the launcher and the timing "
                          "protocol on CPU ranks (gloo).  Never used for a reported number.")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gan_type != "dcgan":
         args.no_roofline = args.no_cpu_baseline = args.no_extras = True
     if args.api_path or args.precision != "bf16" or args.batch != 64:
@@ -414,6 +419,8 @@ def main(argv=None):
     ms_per_step = dt / args.steps * 1e3
     value = N * world * args.steps / dt
     log("timed region: %.3f ms/step, %.1f imgs/s" % (ms_per_step, value))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ls, info)       # before the roofline pass and the extras run further steps
 
     backend = torch.distributed.get_backend() if world > 1 or (torch.distributed.is_available() and
                                                                 torch.distributed.is_initialized()) else None
@@ -482,6 +489,38 @@ def main(argv=None):
     barrier()
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 18       # --dump-outputs: elements written of a larger tensor
+
+
+def dump_outputs(path, losses, info):
+    """--dump-outputs DIR: what the last timed step computed, as its caller receives it -- the loss values the step returned
+    (losses.npy) and the state it leaves behind, every floating-point parameter and buffer of the generator and the
+    discriminator (G.<state_dict key>.npy, D.<key>.npy) -- in float32, or float64 where the tensor is.  A tensor of more
+    than DUMP_SAMPLE elements is written as DUMP_SAMPLE of its flattened elements, at ascending positions drawn by a numpy
+    generator seeded with the element count: the same positions in every run.  Rank 0's values in a data-parallel run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    if losses is not None:
+        arrays["losses"] = torch.stack([l.detach().reshape(()) for l in losses])
+    for net in ("G", "D"):
+        mod = info.get("handles", {}).get(net)
+        if mod is not None:
+            for k, t in mod.state_dict().items():
+                if t.is_floating_point():
+                    arrays["%s.%s" % (net, k)] = t.detach()
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        arrays[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "dump of %d bytes" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("dumped %d arrays (%.1f MB) to %s" % (len(arrays), total / 2 ** 20, path))
 
 
 def measure_roofline(ops, device, one_step, step_ms, extra_ops=()):

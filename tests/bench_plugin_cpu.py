@@ -44,6 +44,6 @@ def make(args, rank, world, device):
 
     # replicas must stay identical across ranks (same seed, all-reduced gradients): checked by the test through the
     # checksum rank 0 prints in the JSON line
-    info = {"workload": "toy CPU twin (test hook)", "rna_features": None,
+    info = {"workload": "toy CPU twin (test hook)", "rna_features": None, "handles": {"G": G, "D": D},
             "param_checksum": lambda: float(sum(p.double().sum() for p in list(G.parameters()) + list(D.parameters())))}
     return one_step, flush, n, info

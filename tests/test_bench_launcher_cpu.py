@@ -46,3 +46,61 @@ def test_failing_rank_fails_the_launch():
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--step-plugin", "tests.bench_plugin_cpu:does_not_exist"])
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss values (those of the JSON line) and the trained parameters and buffers
+    as float .npy files; two runs with the same arguments write the same arrays, and --steps sets how many steps ran."""
+    import numpy as np
+
+    def dump(tag, steps):
+        d = tmp_path / tag
+        r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--step-plugin", "tests.bench_plugin_cpu:make",
+                  "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == steps and out["ms_per_step"] > 0
+        arrays = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert np.array_equal(arrays["losses"], np.array(out["config"]["losses_last_step"]))
+        assert "G.model.0.0.weight" in arrays and "D.disc.0.weight" in arrays
+        return arrays
+
+    a, b, c = dump("a", 3), dump("b", 3), dump("c", 2)
+    assert sorted(a) == sorted(b) == sorted(c)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert not np.array_equal(a["losses"], c["losses"]) and not np.array_equal(a["G.model.0.0.weight"], c["G.model.0.0.weight"])
+
+
+def test_dump_outputs_samples_large_tensors(tmp_path, monkeypatch):
+    """dump_outputs with DUMP_SAMPLE lowered: a tensor above it is written as DUMP_SAMPLE of its elements at ascending,
+    distinct positions, the same positions in every call (the values here ARE the positions); a smaller tensor whole, in its
+    shape; float64 stays float64, bf16 and fp32 are written as float32; integer buffers are left out."""
+    import numpy as np
+    import torch
+    # importing bench.py sets this variable in os.environ: the test leaves the environment as it found it
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    G, D = torch.nn.Module(), torch.nn.Module()
+    G.big = torch.nn.Parameter(torch.arange(1000, dtype=torch.float32).reshape(10, 100))
+    G.register_buffer("small", torch.arange(48, dtype=torch.float64).reshape(6, 8))
+    D.register_buffer("h16", torch.arange(200).to(torch.bfloat16))          # integers up to 256 are exact in bf16
+    D.register_buffer("count", torch.tensor(3))
+    info = {"handles": {"G": G, "D": D}}
+    losses = [torch.tensor(1.5), torch.tensor([2.5]), torch.tensor(-0.25)]
+    dumps = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        bench.dump_outputs(str(d), losses, info)
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    a, b = dumps
+    assert sorted(a) == ["D.h16", "G.big", "G.small", "losses"]
+    assert a["losses"].dtype == np.float32 and a["losses"].tolist() == [1.5, 2.5, -0.25]
+    assert a["G.small"].dtype == np.float64 and np.array_equal(a["G.small"], np.arange(48.0).reshape(6, 8))
+    for name, numel in (("G.big", 1000), ("D.h16", 200)):
+        v = a[name]
+        assert v.dtype == np.float32 and v.shape == (64,)
+        assert np.all(np.diff(v) > 0) and v[0] >= 0 and v[-1] < numel and np.array_equal(v, np.round(v))
+        assert v[-1] >= 64                                  # spread over the tensor, not its first elements
+    assert all(np.array_equal(a[k], b[k]) for k in a)

@@ -36,7 +36,7 @@ from rna_gan_amd import dist as D_, losses as PL
 import rna_gan_amd as P
 from oracle import ref_cpu as R
 rank = int(os.environ["RANK"])
-torch.cuda.set_device(0)
+torch.cuda.set_device(int(os.environ["LOCAL_RANK"]))
 D_.init_from_env(backend="gloo")
 assert D_.world_size() == int(os.environ["WORLD_SIZE"]) and D_.active()
 precision = os.environ["PRECISION"]
@@ -84,14 +84,29 @@ def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
+# Rank r runs on device r % (visible devices).  At most SHARED_WORLD rank processes share one device: with the test process,
+# the eight ranks of a world of 8 on one device are more processes holding a GPU than a shared host admits
+SHARED_WORLD = 4
+
+
+def _require_devices(world):
+    """Called before any work: enough devices that none holds more than SHARED_WORLD ranks."""
+    found = torch.cuda.device_count()
+    need = -(-world // SHARED_WORLD)
+    if found < need:
+        pytest.skip("needs %d GPUs, found %d" % (need, found))
+
+
 def _run_world(tmp_path, precision, world=2, n=N, iters=ITERS, extra_env=None, tag=""):
+    _require_devices(world)
+    ndev = torch.cuda.device_count()
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = str(tmp_path / ("dp%d_%s%s_rank" % (world, precision, tag)))
     port = _free_port()
     procs = []
     for rank in range(world):
         env = dict(os.environ, REPO=repo, OUT=out, PRECISION=precision, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), RNAGAN_FORCE_DP="0",
+                   RANK=str(rank), LOCAL_RANK=str(rank % ndev), WORLD_SIZE=str(world), RNAGAN_FORCE_DP="0",
                    SHAPE="%d,%d,%d,%d,%d" % (IN_SIZE, STEP, ENC, n, iters))
         env.update(extra_env or {})
         procs.append(subprocess.Popen([sys.executable, "-c", WORKER], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
@@ -308,12 +323,13 @@ def test_world2_whole_route(tmp_path, precision):
 
 @pytest.mark.parametrize("world", [4, 8])
 def test_world4_and_world8_plugins_match_ddp_semantics(tmp_path, world):
-    """nothing above world size 2 had ever executed.  4 and 8 rank processes share the box's GPU
-    (gloo, device tensors staged through the host) and run the product's data-parallel route -- graph(prefix) / flush /
+    """nothing above world size 2 had ever executed.  4 or 8 rank processes, at most 4 per device
+    (gloo, device tensors staged through the host), run the product's data-parallel route -- graph(prefix) / flush /
     graph(rest) / eager all-reduce start, 1 / world in the backward seed, rank-local BatchNorm statistics, the paired-weight-
     gradient D-loss prefix -- for two iterations at 4 samples per rank, fp32 kernels and wire: every rank's loss values against
     DistributedDataParallel semantics emulated on the CPU oracle (world replicas, gradients averaged, one Adam step), the
     parameter updates' direction, the rank-local running statistics, and bit-identical parameters on ALL ranks."""
+    _require_devices(world)
     n, iters = 4, 2
     res = _run_world(tmp_path, "fp32", world, n, iters)
     Gs, Ds, want_losses = _ddp_oracle(world, n, iters)
@@ -350,10 +366,12 @@ def test_world4_and_world8_plugins_match_ddp_semantics(tmp_path, world):
 
 
 def test_world8_bf16_kernels_wire_and_gathered_factors(tmp_path):
-    """8 ranks, bf16 kernels, the bf16 wire (when this gloo build reduces bfloat16) and generator layer 0's gradient as
-    all-gathered factors with K = 8 x n samples (dist.G0_FACTORS; the fused G.0 gradient + Adam kernel contracts over all
-    ranks' samples): all ranks bit-identical, losses and weights within the bf16 tolerances of the fp32 run of the same world."""
+    """8 ranks, at most 4 per device, bf16 kernels, the bf16 wire (when this gloo build reduces bfloat16) and generator layer
+    0's gradient as all-gathered factors with K = 8 x n samples (dist.G0_FACTORS; the fused G.0 gradient + Adam kernel
+    contracts over all ranks' samples): all ranks bit-identical, losses and weights within the bf16 tolerances of the fp32
+    run of the same world."""
     n, iters, world = 4, 2, 8
+    _require_devices(world)
     f32 = _run_world(tmp_path, "fp32", world, n, iters)
     b16 = _run_world(tmp_path, "bf16", world, n, iters)
     print("all-reduce wire of the 8-rank bf16 run:", b16[0]["wire"], "factor buffers (rows):", b16[0]["factor_rows"])

@@ -738,18 +738,22 @@ def _fp8_conv_up_and_gemm_body(hip, N, Ho, O, I, out_fp8):
     _, ch = cwpair_tm(w)
     x8 = hip.cast_fp8(rnd((N, Ho, Ho, O), 2).cuda())
     scale, shift = 1 + 0.1 * rnd((I,), 3), 0.1 * rnd((I,), 4)
-    if not hip.fp8_supported(N * Ho * Ho, 4 * O, I, 4):
-        pytest.skip("no fp8 kernel for this shape")
-    y = hip.conv_up_fp8(x8, ch, scale.cuda(), shift.cuda(), 0.2, out_fp8)
-    q, s = hip.fp8_pack_up(ch)
-    wq = _fp8_decode(q).reshape(4, 4, I, O) * s.cpu()[None, None, :, None]           # dequantised [kh][kw][i][o]
-    ref = F.conv_transpose2d(_fp8_decode(x8).permute(0, 3, 1, 2), wq.permute(3, 2, 0, 1), stride=2, padding=1)
-    ref = ref.permute(0, 2, 3, 1) * scale + shift
-    ref = torch.where(ref > 0, ref, 0.2 * ref)
-    got = _fp8_decode(y) if out_fp8 else y.float().cpu()
     tol = 0.07 if out_fp8 else 1.2e-2                       # one e4m3 (3 mantissa bits) / one bf16 rounding of the output
-    assert float((got - ref).abs().max()) <= tol * float(ref.abs().max())
-    assert float((wq - w.permute(2, 3, 1, 0)).abs().max()) <= 0.07 * float(w.abs().max())     # weight quantisation itself
+    q, s = hip.fp8_pack_up(ch)
+    wq = _fp8_decode(q).reshape(4, 4, I, O) * s.cpu()[None, None, :, None]               # dequantised [kh][kw][i][o]
+    assert float((wq - w.permute(2, 3, 1, 0)).abs().max()) <= 0.07 * float(w.abs().max())         # weight quantisation itself
+    if hip.fp8_supported(N * Ho * Ho, 4 * O, I, 4):
+        y = hip.conv_up_fp8(x8, ch, scale.cuda(), shift.cuda(), 0.2, out_fp8)
+        ref = F.conv_transpose2d(_fp8_decode(x8).permute(0, 3, 1, 2), wq.permute(3, 2, 0, 1), stride=2, padding=1)
+        ref = ref.permute(0, 2, 3, 1) * scale + shift
+        ref = torch.where(ref > 0, ref, 0.2 * ref)
+        got = _fp8_decode(y) if out_fp8 else y.float().cpu()
+        assert float((got - ref).abs().max()) <= tol * float(ref.abs().max())
+    else:
+        # no fp8 kernel for this shape (128 output columns need at least 512 low-resolution pixels): the entry point refuses
+        # it with an error before any launch, and engine.gen_forward_eval_fp8 keeps such a layer on the bf16 kernels
+        with pytest.raises(RuntimeError, match=r"rg_conv_up_fp8 failed \(-2\).*shape not supported"):
+            hip.conv_up_fp8(x8, ch, scale.cuda(), shift.cuda(), 0.2, out_fp8)
     # plain GEMM: M rows x K, B[(tap, c)][E]
     M, E, C = 256, 512, 32
     g0 = ConvW(rnd((E, C, 4, 4), 7, (2.0 / E) ** 0.5).cuda())
