@@ -70,6 +70,8 @@ EXTRA_FLAGS = [
     ("--precision", str, "bf16", "bf16 (MFMA kernels), fp16 (the same kernels built for IEEE fp16 storage, loss-scaled backward) or fp32 (parity mode)"),
     ("--betavae_checkpoint", str, "checkpoints/betavae_training_tissues/model_dict_best.pt", "frozen betaVAE weights"),
     ("--steps_per_epoch", int, 100, "synthetic dataset length / batch"),
+    ("--loss_scaling", str, "static", "fp16 only: static (fixed scale RNAGAN_F16_LOSS_SCALE) or dynamic (GradScaler-style: a step "
+                                      "with a non-finite gradient is skipped and the scale halved; it grows after clean steps)"),
 ]
 
 
@@ -109,6 +111,10 @@ def main():
     args = parse_args()
     if args.precision not in ("bf16", "fp32", "fp16"):
         raise SystemExit("--precision must be bf16, fp16 or fp32")
+    if args.loss_scaling not in ("static", "dynamic"):
+        raise SystemExit("--loss_scaling must be static or dynamic")
+    if args.loss_scaling == "dynamic" and args.precision != "fp16":
+        raise SystemExit("--loss_scaling dynamic applies to --precision fp16 only")
 
     D_.set_sync_stats(bool(args.sync_stats))
     D_.init_from_env()
@@ -188,7 +194,7 @@ def main():
     epochs = args.num_epochs if args.num_epochs is not None else 5
     print("Device: {}".format(device)); print("Epochs: {}".format(epochs))
     trainer = P.Trainer(gan_network, losses, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
-                        recon=args.image_dir, device=device, precision=args.precision)
+                        recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling)
     if args.checkpoint is not None:
         trainer.load_model(load_path=args.checkpoint)
     for loss in losses:                                   # identical frozen encoders on every rank (rank 0's)

@@ -207,6 +207,9 @@ int rg_gp_coef_parts(const float* part, int nblocks, float* sq, float* loss, flo
  * out_scale.  Scales are powers of two (exact); with in_scale = out_scale = 1 this is rg_gp_coef_parts bit for bit. */
 int rg_gp_coef_parts_scaled(const float* part, int nblocks, float* sq, float* loss, float* coef, float lambd, float in_scale,
                             float out_scale, void* stream);
+/* ... with in_scale = 2^floor(k/2), out_scale = 2^(k - floor(k/2)) for the exponent latched for `slot` (rg_amp_latch) */
+int rg_gp_coef_parts_scaled_dev(const float* part, int nblocks, float* sq, float* loss, float* coef, float lambd,
+                                const int* amp_state, int slot, void* stream);
 /* rg_last_up with the generator's last train-mode BatchNorm + LeakyReLU applied to its input on the fly (z = the pre-BatchNorm
  * conv output; mean / invstd from rg_bn_finalize_partials or rg_bn_stats_finalize): the no-grad generator forwards of the
  * D-loss and penalty steps (src/wgan_loss.py:247,371) skip the normalisation pass over their largest activation.  Same bf16
@@ -254,6 +257,10 @@ int rg_head_fwd(const void* a, const float* w, float* h, float* out, int N, int 
                 void* stream);
 /* gh[n] = coef * lrelu'(h[n])  (coef = d loss / d out[n]: -1/N, +1/N or 1; wgan_loss.py:24-29,33) */
 int rg_head_grad(const float* h, float* gh, int N, float coef, float slope, void* stream);
+/* the same with coef * 2^e, e from the exponent latched for `slot` (rg_amp_latch): part 0: e = k, 1: floor(k / 2) (the penalty's
+ * first backward), 2: k - floor(k / 2) */
+int rg_head_grad_dev(const float* h, float* gh, int N, float coef, const int* amp_state, int slot, int part, float slope,
+                     void* stream);
 int rg_head_bwd_data(const float* gh, const float* w, void* ga, int N, int C, int dtype, void* stream);
 int rg_head_wgrad(const float* gh, const void* a, float* dw, int N, int C, int dtype, int accumulate,
                   void* stream);
@@ -468,6 +475,7 @@ int rg_sqnorm(const float* x, float* out, size_t n, void* ws, size_t ws_bytes, v
 /* from sq = ||g||^2: loss = (sqrt(sq)-1)^2 ; coef = lambd*2*(sqrt(sq)-1)/sqrt(sq) (wgan_loss.py:43) */
 int rg_gp_coef(const float* sq, float* loss, float* coef, float lambd, void* stream);
 int rg_gp_coef_scaled(const float* sq, float* loss, float* coef, float lambd, float in_scale, float out_scale, void* stream);
+int rg_gp_coef_scaled_dev(const float* sq, float* loss, float* coef, float lambd, const int* amp_state, int slot, void* stream);
 /* out = x * coef[0] (coef on device: no host sync inside the step) */
 int rg_scale_by(const float* x, const float* coef, float* out, size_t n, void* stream);
 /* out[0] = sign * mean(a - b) (b may be NULL) (wgan_loss.py:24-29) */
@@ -527,6 +535,35 @@ int rg_adam_hyper_dev(int* step_dev, double lr, double beta1, double beta2, doub
  * therefore >= 9 floats for BOTH entry points; rg_adam_hyper_dev writes hyper[8] = 1 (exact: results unchanged). */
 int rg_adam_hyper_dev2(int* step_dev, double lr, double beta1, double beta2, double eps, double weight_decay,
                        double grad_scale_inv, float* hyper, void* stream);
+/* The hyper buffer is 12 floats: [0..8] as above, [9] = the SKIP WORD -- every kernel that applies an Adam update from `hyper`
+ * (rg_adam_step_dev and its scalar form, rg_adam_step_slabs, rg_g0_wgrad_adam, rg_conv_wgrad_adam, rg_linear_wgrad_adam)
+ * returns at once, touching nothing, when it is non-zero; rg_adam_hyper_dev / _dev2 write 0.  [10..11] unused.
+ *
+ * DYNAMIC LOSS SCALING (opt-in, rna_gan_amd.amp; rna_gan_amd/csrc/rg_amp.hip).  State: int32[RG_AMP_STATE_INTS] on the device:
+ *   [RG_AMP_EXP] k with scale S = 2^k, [RG_AMP_TRACKER] finite steps since the last change, [RG_AMP_SKIPPED] skipped steps,
+ *   [RG_AMP_LATCH + slot] k as latched at the first backward seed of the last train_op that steps network `slot`,
+ *   [RG_AMP_FLAG + slot] non-zero when a probe of that network's step found a non-finite value.
+ * rg_adam_hyper_dev3: rg_adam_hyper_dev2 with grad_scale_inv = 2^-latch[slot] and hyper[9] = flag[slot]; when the flag is set the
+ *   step counter is NOT advanced (a skipped step does not count) and hyper[0..6] are left as they were. */
+#define RG_AMP_EXP 0
+#define RG_AMP_TRACKER 1
+#define RG_AMP_SKIPPED 2
+#define RG_AMP_LATCH 4
+#define RG_AMP_FLAG 8
+#define RG_AMP_SLOTS 4
+#define RG_AMP_STATE_INTS 12
+int rg_adam_hyper_dev3(int* step_dev, double lr, double beta1, double beta2, double eps, double weight_decay,
+                       const int* amp_state, int slot, float* hyper, void* stream);
+/* OR "any non-finite value" into *flag: nseg <= 32 segments (HOST arrays) of seg_n[i] elements at seg_ptr[i], fp32 or this build's
+ * 16-bit type by seg_dtype[i] (element-aligned; any length).  Exponent-mask test on the raw bits (fp32 0x7f800000, fp16 0x7c00,
+ * bf16 0x7f80), wave-level OR, one atomic per wave that found something; nothing is written otherwise. */
+int rg_nonfinite_probe(int nseg, const void* const* seg_ptr, const unsigned long long* seg_n, const int* seg_dtype, int* flag,
+                       void* stream);
+/* after the Adam launches of network `slot`: flag set -> k = max(k - 1, min_exp), tracker = 0, skipped += 1; flag clear ->
+ * tracker += 1 and, when it reaches growth_interval, k = min(k + 1, max_exp), tracker = 0.  Then flag[slot] = 0. */
+int rg_amp_update(int* amp_state, int slot, int growth_interval, int min_exp, int max_exp, void* stream);
+/* latch[slot] = k: enqueued before the first backward seed of a train_op that steps network `slot` */
+int rg_amp_latch(int* amp_state, int slot, void* stream);
 /* The 16-bit storage type of this build of the library: RG_BF16 (librnagan_hip.so) or RG_F16 (librnagan_hip_f16.so: the same
  * sources compiled with -DRG_HALF_F16 -- activations, operand images, split-K slabs and the data-parallel wire are IEEE fp16,
  * the MFMAs the _f16 forms; every entry point takes RG_F16 where this header says RG_BF16; no rg_probe_* entry points).

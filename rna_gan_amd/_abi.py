@@ -58,6 +58,13 @@ PROTOTYPES = {
     "rg_g0_wgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
     "rg_head_fwd": (_i, [_p, _p, _p, _p, _i, _i, _f, _i, _p]),
     "rg_head_grad": (_i, [_p, _p, _i, _f, _f, _p]),
+    "rg_head_grad_dev": (_i, [_p, _p, _i, _f, _p, _i, _i, _f, _p]),
+    "rg_adam_hyper_dev3": (_i, [_p, _d, _d, _d, _d, _d, _p, _i, _p, _p]),
+    "rg_nonfinite_probe": (_i, [_i, _p, _p, _p, _p, _p]),
+    "rg_amp_update": (_i, [_p, _i, _i, _i, _i, _p]),
+    "rg_amp_latch": (_i, [_p, _i, _p]),
+    "rg_gp_coef_scaled_dev": (_i, [_p, _p, _p, _f, _p, _i, _p]),
+    "rg_gp_coef_parts_scaled_dev": (_i, [_p, _i, _p, _p, _p, _f, _p, _i, _p]),
     "rg_head_bwd_data": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "rg_head_wgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "rg_pack_linear_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
@@ -179,7 +186,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES
-ABI_VERSION = 600
+ABI_VERSION = 610
 
 _libs = {}
 LIB_PATH_F16 = os.path.join(_HERE, "librnagan_hip_f16.so")

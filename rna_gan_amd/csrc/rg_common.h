@@ -255,7 +255,8 @@ __device__ __forceinline__ void up_taps(int u, int L, int& i0, int& i1, float& l
 // expression, so that a tensor stepped by any of them comes out bit-identical.  hyper[0..7] = b1, b2, 1 - b1, 1 - b2, eps,
 // lr / bc1, 1 / sqrt(bc2), weight decay (rg_adam_hyper_dev); hyper[8] = 1 / loss scale: the factor every kernel applies to the
 // gradient it reads before the update (1 except in the fp16 build's loss-scaled backward; a multiplication by 1.0f is exact, so the
-// unscaled paths are bit for bit what they were).
+// unscaled paths are bit for bit what they were); hyper[9] = skip word: non-zero when the step is skipped (rg_adam_hyper_dev3 found a
+// non-finite gradient), and every kernel that applies the update then returns at once (0 from rg_adam_hyper_dev / _dev2).
 __device__ __forceinline__ void rg_adam_upd(float& pp, float gg, float& mm, float& vv, float b2, float omb1, float omb2, float eps,
                                             float step_size, float inv_sqrt_bc2, float wd) {
   if (wd != 0.f) gg += wd * pp;               // torch.optim.Adam weight_decay (L2 on the gradient); betaVAE training
@@ -275,6 +276,15 @@ struct RgAdamHyper {
     rg_adam_upd(pp, gg * ginv, mm, vv, b2, omb1, omb2, eps, step_size, inv_sqrt_bc2, wd);
   }
 };
+
+// ---- dynamic loss scaling (rg_amp.hip; layout of the int32 state in include/rnagan_hip.h, RG_AMP_*): the scale is S = 2^k with
+// the exponent k in device memory.  The penalty's first backward seed is 2^floor(k/2) and its tangent direction carries
+// 2^(k - floor(k/2)): in_inv / out_scale of the coefficient kernels (gp_coef_kernel; for k = 12 the static 64 / 64 split).
+__device__ __forceinline__ void rg_gp_scales_from_exp(int k, float& in_inv, float& out_scale) {
+  const int ks = k >> 1;                      // floor(k / 2), negative k included
+  in_inv = ldexpf(1.f, -ks);
+  out_scale = ldexpf(1.f, k - ks);
+}
 
 // dtype dispatch helper for host code
 #define RG_DISPATCH_DTYPE(dtype, T, ...)                                  \

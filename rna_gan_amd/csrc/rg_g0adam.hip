@@ -41,6 +41,7 @@ __global__ __launch_bounds__(256) void g0_wgrad_adam_kernel(const float* __restr
   constexpr int OPS = (GA_E + GA_J) * GA_P * 2;                       // 46080 B of operand images
   static_assert(32 * GA_CP * 4 <= OPS, "accumulator tile must fit into the operand area");
   __shared__ __attribute__((aligned(16))) unsigned char smem[OPS];
+  if (hyper[9] != 0.f) return;                                       // skipped step (rg_adam_hyper_dev3)
   uint16_t* zsT = reinterpret_cast<uint16_t*>(smem);                  // [64 e][GA_P]
   uint16_t* gsT = zsT + GA_E * GA_P;                                  // [256 j][GA_P]
   float* ct = reinterpret_cast<float*>(smem);                         // [32 e][GA_CP] fp32 = 33 KB, after the k loop
@@ -199,6 +200,7 @@ __global__ __launch_bounds__(256) void lin_wgrad_adam_kernel(const uint16_t* __r
                                                              int I, uint16_t* __restrict__ wpack, int Kp) {
   constexpr int OPS = (GA_E + GA_J) * GA_P * 2;
   __shared__ __attribute__((aligned(16))) unsigned char smem[OPS];
+  if (hyper[9] != 0.f) return;                                       // skipped step (rg_adam_hyper_dev3)
   uint16_t* zsT = reinterpret_cast<uint16_t*>(smem);                  // [64 o][GA_P]
   uint16_t* gsT = zsT + GA_E * GA_P;                                  // [256 i][GA_P]
   float* ct = reinterpret_cast<float*>(smem);

@@ -100,6 +100,7 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
                                                        float* __restrict__ m, float* __restrict__ v,
                                                        const float* __restrict__ hyper, uint16_t* __restrict__ shadow,
                                                        const uint16_t* __restrict__ gw, size_t n) {
+  if (hyper[9] != 0.f) return;                             // skipped step (rg_adam_hyper_dev3)
   const Adam a{p, g, m, v, hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], hyper[7], hyper[8]};
   const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x;
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
@@ -203,6 +204,7 @@ __global__ __launch_bounds__(256) void adam_segs_kernel(float* __restrict__ p, c
                                                         const float* __restrict__ hyper, uint16_t* __restrict__ shadow,
                                                         AdamSegs t) {
   __shared__ float4 sm[16][64];                            // [slab lane][column]: SL = 4 uses [4][64], SL = 16 [16][16]
+  if (hyper[9] != 0.f) return;                             // skipped step (rg_adam_hyper_dev3)
   const Adam a{p, g, m, v, hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], hyper[7], hyper[8]};
   for (int si = 0; si < t.nseg; ++si) {
     const AdamSeg sg = t.s[si];
@@ -318,20 +320,35 @@ __global__ __launch_bounds__(256) void wire_segs_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void adam_dev_scalar_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ m, float* __restrict__ v,
                                                               const float* __restrict__ hyper, size_t n) {
+  if (hyper[9] != 0.f) return;                             // skipped step (rg_adam_hyper_dev3)
   const Adam a{p, g, m, v, hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[6], hyper[7], hyper[8]};
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     a.upd(p[i], g[i], m[i], v[i]);
 }
 
-__global__ void adam_hyper_kernel(int* step_dev, double lr, double b1, double b2, double eps, double wd, double ginv, float* hyper) {
-  hyper[7] = (float)wd;
-  hyper[8] = (float)ginv;
+__device__ __forceinline__ void adam_hyper_advance(int* step_dev, double lr, double b1, double b2, double eps, float* hyper) {
   int step = *step_dev + 1;
   *step_dev = step;
   double bc1 = 1.0 - pow(b1, (double)step);
   double bc2 = 1.0 - pow(b2, (double)step);
   hyper[0] = (float)b1; hyper[1] = (float)b2; hyper[2] = (float)(1.0 - b1); hyper[3] = (float)(1.0 - b2);
   hyper[4] = (float)eps; hyper[5] = (float)(lr / bc1); hyper[6] = (float)(1.0 / sqrt(bc2));
+}
+__global__ void adam_hyper_kernel(int* step_dev, double lr, double b1, double b2, double eps, double wd, double ginv, float* hyper) {
+  hyper[7] = (float)wd;
+  hyper[8] = (float)ginv;
+  hyper[9] = 0.f;                                          // never a skipped step
+  adam_hyper_advance(step_dev, lr, b1, b2, eps, hyper);
+}
+// dynamic loss scaling (rg_amp.hip): 1 / the scale latched for this slot, the skip word from its non-finite flag; a skipped step
+// leaves the step counter (and with it the bias corrections of the next step) where it was
+__global__ void adam_hyper3_kernel(int* step_dev, double lr, double b1, double b2, double eps, double wd, const int* amp,
+                                   int slot, float* hyper) {
+  const int skip = amp[RG_AMP_FLAG + slot] != 0;
+  hyper[7] = (float)wd;
+  hyper[8] = ldexpf(1.f, -amp[RG_AMP_LATCH + slot]);
+  hyper[9] = skip ? 1.f : 0.f;
+  if (!skip) adam_hyper_advance(step_dev, lr, b1, b2, eps, hyper);
 }
 
 // ---------------------------------------------------------------------------------- reductions
@@ -390,7 +407,9 @@ __global__ void nchw_chan_final_kernel(const float* partial, float* out, int C, 
 
 // in_inv = 1 / (the scale the gradient whose squared norm is sq carries), out_scale = the scale the tangent direction is to
 // carry (both 1 outside the fp16 build's loss-scaled penalty step; powers of two, so exact)
-__global__ void gp_coef_kernel(const float* sq, float* loss, float* coef, float lambd, float in_inv, float out_scale) {
+__global__ void gp_coef_kernel(const float* sq, float* loss, float* coef, float lambd, float in_inv, float out_scale,
+                               const int* scale_exp) {
+  if (scale_exp) rg_gp_scales_from_exp(*scale_exp, in_inv, out_scale);      // dynamic loss scaling: the train_op's latched 2^k
   float nrm = sqrtf(sq[0]) * in_inv;
   loss[0] = (nrm - 1.f) * (nrm - 1.f);
   coef[0] = lambd * 2.f * (nrm - 1.f) / nrm * (in_inv * out_scale);
@@ -710,6 +729,22 @@ extern "C" int rg_adam_hyper_dev2(int* step_dev, double lr, double beta1, double
   RG_LAUNCH_CHECK("adam_hyper_dev");
   return RG_OK;
 }
+extern "C" int rg_adam_hyper_dev3(int* step_dev, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                  const int* amp_state, int slot, float* hyper, void* stream) {
+  RG_REQUIRE(step_dev && hyper && amp_state && slot >= 0 && slot < RG_AMP_SLOTS, RG_EINVAL, "adam_hyper_dev3: bad args");
+  hipLaunchKernelGGL(adam_hyper3_kernel, dim3(1), dim3(1), 0, rg_stream(stream), step_dev, lr, beta1, beta2, eps, weight_decay,
+                     amp_state, slot, hyper);
+  RG_LAUNCH_CHECK("adam_hyper_dev3");
+  return RG_OK;
+}
+extern "C" int rg_gp_coef_scaled_dev(const float* sq, float* loss, float* coef, float lambd, const int* amp_state, int slot,
+                                     void* stream) {
+  RG_REQUIRE(sq && loss && coef && amp_state && slot >= 0 && slot < RG_AMP_SLOTS, RG_EINVAL, "gp_coef_dev: bad args");
+  hipLaunchKernelGGL(gp_coef_kernel, dim3(1), dim3(1), 0, rg_stream(stream), sq, loss, coef, lambd, 1.f, 1.f,
+                     amp_state + RG_AMP_LATCH + slot);
+  RG_LAUNCH_CHECK("gp_coef_dev");
+  return RG_OK;
+}
 extern "C" int rg_adam_hyper_dev(int* step_dev, double lr, double beta1, double beta2, double eps, double weight_decay,
                                  float* hyper, void* stream) {
   return rg_adam_hyper_dev2(step_dev, lr, beta1, beta2, eps, weight_decay, 1.0, hyper, stream);
@@ -755,13 +790,14 @@ extern "C" int rg_nchw_chan_sum(const float* g, float* out, int N, int C, int HW
 extern "C" int rg_gp_coef_scaled(const float* sq, float* loss, float* coef, float lambd, float in_scale, float out_scale,
                                  void* stream) {
   RG_REQUIRE(sq && loss && coef && in_scale > 0.f && out_scale > 0.f, RG_EINVAL, "gp_coef: bad args");
-  hipLaunchKernelGGL(gp_coef_kernel, dim3(1), dim3(1), 0, rg_stream(stream), sq, loss, coef, lambd, 1.f / in_scale, out_scale);
+  hipLaunchKernelGGL(gp_coef_kernel, dim3(1), dim3(1), 0, rg_stream(stream), sq, loss, coef, lambd, 1.f / in_scale, out_scale,
+                     nullptr);
   RG_LAUNCH_CHECK("gp_coef");
   return RG_OK;
 }
 extern "C" int rg_gp_coef(const float* sq, float* loss, float* coef, float lambd, void* stream) {
   RG_REQUIRE(sq && loss && coef, RG_EINVAL, "gp_coef: bad args");
-  hipLaunchKernelGGL(gp_coef_kernel, dim3(1), dim3(1), 0, rg_stream(stream), sq, loss, coef, lambd, 1.f, 1.f);
+  hipLaunchKernelGGL(gp_coef_kernel, dim3(1), dim3(1), 0, rg_stream(stream), sq, loss, coef, lambd, 1.f, 1.f, nullptr);
   RG_LAUNCH_CHECK("gp_coef");
   return RG_OK;
 }

@@ -584,8 +584,9 @@ __global__ __launch_bounds__(256, 2) void last_up_rows_kernel(const uint16_t* __
 // or the penalty's coefficient from sq = sum_b part[b][3] (mode 1: gp_coef_kernel's arithmetic)
 __global__ __launch_bounds__(256) void lu_part_final_kernel(const float* __restrict__ part, int nb, float* out, int accumulate,
                                                             int mode, float* loss, float* coef, float lambd, float in_inv,
-                                                            float out_scale) {
+                                                            float out_scale, const int* scale_exp) {
   __shared__ float sm[4][4];
+  if (scale_exp) rg_gp_scales_from_exp(*scale_exp, in_inv, out_scale);      // dynamic loss scaling (rg_gp_coef_parts_scaled_dev)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   for (int b = t; b < nb; b += 256) {
@@ -1384,9 +1385,9 @@ int rg_skinny_last_up_post_blocks(int N, int Ho, int Wo, int O, int dtype) {
   return nstrips < 512 ? (int)nstrips : 512;
 }
 int rg_skinny_lu_part_final(const float* part, int nb, float* out, int accumulate, int mode, float* loss, float* coef,
-                            float lambd, hipStream_t st, float in_scale, float out_scale) {
+                            float lambd, hipStream_t st, float in_scale, float out_scale, const int* scale_exp) {
   hipLaunchKernelGGL(lu_part_final_kernel, dim3(1), dim3(256), 0, st, part, nb, out, accumulate, mode, loss, coef, lambd,
-                     1.f / in_scale, out_scale);
+                     1.f / in_scale, out_scale, scale_exp);
   RG_LAUNCH_CHECK("last_up_post_final");
   return RG_OK;
 }

@@ -76,6 +76,9 @@ __global__ __launch_bounds__(512, 2) void wgrad8_kernel(W8Args g) {
   constexpr int OFF_B = 0, OFF_A = 2 * HT;
   constexpr int LDS_BYTES = 2 * STAGE;             // 128 KB
   __shared__ __attribute__((aligned(16))) uint4 lds[LDS_BYTES / 16];
+  if constexpr (ADAM) {
+    if (g.hyper[9] != 0.f) return;                 // the step is skipped (non-finite gradient, rg_adam_hyper_dev3): no tile, no update
+  }
 
   const int t = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);

@@ -218,7 +218,7 @@ def disc_forward(ops, D: DiscNet, x_nchw, update_running=True):
 
 
 def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
-                  need_input_grad: bool, keep_for_gp: bool = False, input_post=None, partner=None):
+                  need_input_grad: bool, keep_for_gp: bool = False, input_post=None, partner=None, seed_part: int = 0):
     """Backward of sum_n coef * D(x)_n (coef: a float, or an (N,) tensor of per-sample cotangents as torch autograd
     hands them over).  wgrad: also produce parameter gradients (written with ``accumulate`` semantics into the
     .dw/.dbias/.dgamma/.dbeta buffers).  Returns d/dx (NCHW fp32) if requested.  keep_for_gp stores the per-layer
@@ -229,7 +229,8 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
     wgrad == "defer": the small parameter gradients (head, BatchNorm, layer-0 bias) are produced now, the conv weight
     gradients are NOT -- their operands gz stay on ctx.gz_keep for a later call with partner=ctx, whose per-layer weight
     gradient is then ONE two-segment launch over both chains (written, whatever ``accumulate`` says for the rest): the
-    data-parallel D-loss step's prefix / rest pair (disc_loss_prefix_dgrad / disc_loss_rest_pairw)."""
+    data-parallel D-loss step's prefix / rest pair (disc_loss_prefix_dgrad / disc_loss_rest_pairw).
+    seed_part: under dynamic loss scaling, the power of the device scale the seed carries (ops.head_grad)."""
     R = len(D.blocks)
     defer_w = isinstance(wgrad, str) and wgrad == "defer"
     if defer_w:
@@ -238,6 +239,8 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
     if torch.is_tensor(coef):       # N-length vector: host-side plumbing
         gh = (coef.reshape(-1).float() * torch.where(ctx.h > 0, torch.ones_like(ctx.h),
                                                      torch.full_like(ctx.h, D.last_slope))).contiguous()
+    elif seed_part:
+        gh = ops.head_grad(ctx.h, coef, D.last_slope, part=seed_part)
     else:
         gh = ops.head_grad(ctx.h, coef, D.last_slope)
     if wgrad:
@@ -358,10 +361,12 @@ def disc_gp_first(ops, D: DiscNet, ctx, lambd):
     # fp16 storage (HIP backend): the seed carries ops.gp_seed_scale so that the data gradients stay in fp16's normal range;
     # gp_coef / gp_coef_parts divide the norm by it and put ops.gp_tangent_scale on the tangent direction instead -- the joint
     # reverse sweep is bilinear in (first-backward gradients, tangents), so its parameter gradients arrive scaled by the product
-    # (= the step's loss scale, which the optimizer removes).  1.0 everywhere else.
+    # (= the step's loss scale, which the optimizer removes).  1.0 everywhere else.  Dynamic loss scaling (rna_gan_amd.amp):
+    # the same split of the device scale 2^k, 2^floor(k/2) on the seed (seed_part=1) and the rest on the tangent.
     seed = float(getattr(ops, "gp_seed_scale", 1.0))
+    dyn = getattr(ops, "amp", None) is not None
     g = disc_backward(ops, D, ctx, seed, wgrad=False, accumulate=False, need_input_grad=True, keep_for_gp=True,
-                      input_post=fuse)
+                      input_post=fuse, seed_part=1 if dyn else 0)
     if ctx.gx_parts is not None:
         loss, coef = ops.gp_coef_parts(ctx.gx_parts, lambd)
     else:

@@ -140,6 +140,11 @@ def _nets(generator, discriminator):
     od, dn = discriminator.runtime()
     if og.act_dtype != od.act_dtype:
         raise RuntimeError("generator and discriminator must use the same precision")
+    if getattr(og, "amp", None) is not getattr(od, "amp", None):
+        # every seed is issued through the generator's backend and every optimizer unscales with its own network's: a scaler on
+        # one of them only would leave the other network's gradients off by the scale
+        raise RuntimeError("dynamic loss scaling: attach ONE DynamicLossScaler to both the generator and the discriminator "
+                           "(DynamicLossScaler.attach(G, D))")
     return og, gn, dn
 
 
@@ -168,7 +173,7 @@ def _reduce(module):
 
 def _apply(module, optimizer):
     ops, _ = module.runtime()
-    if ops.loss_scale != 1.0 and getattr(optimizer, "_module", None) is not module:
+    if (ops.loss_scale != 1.0 or getattr(ops, "amp", None) is not None) and getattr(optimizer, "_module", None) is not module:
         # fp16: the gradients in module.flat.grad carry the loss scale; only rna_gan_amd.optim.Adam bound to the module unscales
         raise RuntimeError("fp16 precision needs rna_gan_amd.optim.Adam(...).bind(module): a foreign optimizer would step on "
                            "loss-scaled gradients")
@@ -176,6 +181,23 @@ def _apply(module, optimizer):
     if not hasattr(optimizer, "note_replayed"):      # rna_gan_amd.optim.Adam reports the change itself
         module.weights_changed()
     return module.flat.data[:1]          # a tensor result, so that this half can be a graph of its own
+
+
+# Dynamic loss scaling (rna_gan_amd.amp): the scale is latched for the STEPPED network right before the first backward seed of its
+# train_op -- in the rest, except for a data-parallel D-loss prefix that seeds D(real) -- and the loss is probed for non-finite
+# values once the rest has produced it.  In the data-parallel "prefix" route a network's pending optimizer step (which reads
+# its latch) is always applied before that network's next train_op seeds: the D step's pending update runs in the flush between
+# the penalty step's prefix (which reads G and seeds nothing) and its rest, G's between the D-loss prefix and rest.
+def _amp_latch(ops, stepped):
+    if getattr(ops, "amp", None) is not None:
+        ops.amp.latch(ops, stepped)
+
+
+def _amp_loss(ops, stepped, loss):
+    # (data parallel: the loss is rank-local, so only the all-reduced gradients decide -- every rank decides alike)
+    if getattr(ops, "amp", None) is not None and not D_.active():
+        ops.amp.probe_loss(ops, stepped, loss[0] if isinstance(loss, tuple) else loss)
+    return loss
 
 
 # Every train_op body is  rest(prefix(...))  where the PREFIX reads only ONE of the two networks (engine.*_prefix):
@@ -191,7 +213,8 @@ def _g_prefix(generator, discriminator, noise):
 
 def _g_rest(generator, discriminator, pre):
     ops, gn, dn = _nets(generator, discriminator)
-    return E.gen_loss_rest(ops, gn, dn, pre, grad_scale=D_.grad_scale() * ops.loss_scale)
+    _amp_latch(ops, generator)
+    return _amp_loss(ops, generator, E.gen_loss_rest(ops, gn, dn, pre, grad_scale=D_.grad_scale() * ops.loss_scale))
 
 
 # data-parallel D-loss step: D(real)'s backward belongs to the prefix too (it reads the discriminator only), so the generator's
@@ -230,6 +253,8 @@ def _d_prefix(generator, discriminator, real, noise, clip):
     if clip is not None:
         ops.clamp_(discriminator.flat.data, clip[0], clip[1])      # every D parameter (wgan_loss.py:213-215)
         discriminator.weights_changed()
+    if DP_PREFIX_BWD and D_.active():
+        _amp_latch(ops, discriminator)           # D(real)'s backward is seeded here
     if DP_PREFIX_MODE == 2 and D_.active():
         return ("dgrad", E.disc_loss_prefix_dgrad(ops, dn, real.contiguous().float(), grad_scale=D_.grad_scale() * ops.loss_scale)), \
             noise.contiguous().float()
@@ -246,9 +271,10 @@ def _d_batched(generator, discriminator, real, noise, clip, next_noise=None):
     if clip is not None:
         ops.clamp_(discriminator.flat.data, clip[0], clip[1])
         discriminator.weights_changed()
-    return E.disc_loss_grads_batched(ops, gn, dn, real.contiguous().float(), noise.contiguous().float(),
-                                     grad_scale=D_.grad_scale() * ops.loss_scale,
-                                     next_noise=None if next_noise is None else next_noise.contiguous().float())
+    _amp_latch(ops, discriminator)
+    return _amp_loss(ops, discriminator, E.disc_loss_grads_batched(
+        ops, gn, dn, real.contiguous().float(), noise.contiguous().float(), grad_scale=D_.grad_scale() * ops.loss_scale,
+        next_noise=None if next_noise is None else next_noise.contiguous().float()))
 
 
 class _FakeCache:
@@ -310,10 +336,14 @@ def _d_rest(generator, discriminator, pre):
     ops, gn, dn = _nets(generator, discriminator)
     fwd_real, noise = pre
     if isinstance(fwd_real, tuple) and fwd_real[0] == "bwd":       # the real half's backward ran in the prefix
-        return E.disc_loss_rest_acc(ops, gn, dn, fwd_real[1], noise, grad_scale=D_.grad_scale() * ops.loss_scale)
+        return _amp_loss(ops, discriminator, E.disc_loss_rest_acc(ops, gn, dn, fwd_real[1], noise,
+                                                                  grad_scale=D_.grad_scale() * ops.loss_scale))
     if isinstance(fwd_real, tuple) and fwd_real[0] == "dgrad":     # ... its data-gradient chain did; weight gradients pair up here
-        return E.disc_loss_rest_pairw(ops, gn, dn, fwd_real[1], noise, grad_scale=D_.grad_scale() * ops.loss_scale)
-    return E.disc_loss_rest(ops, gn, dn, fwd_real, noise, grad_scale=D_.grad_scale() * ops.loss_scale)
+        return _amp_loss(ops, discriminator, E.disc_loss_rest_pairw(ops, gn, dn, fwd_real[1], noise,
+                                                                    grad_scale=D_.grad_scale() * ops.loss_scale))
+    _amp_latch(ops, discriminator)
+    return _amp_loss(ops, discriminator, E.disc_loss_rest(ops, gn, dn, fwd_real, noise,
+                                                          grad_scale=D_.grad_scale() * ops.loss_scale))
 
 
 def _gp_prefix(generator, discriminator, real, noise, eps):
@@ -324,7 +354,8 @@ def _gp_prefix(generator, discriminator, real, noise, eps):
 
 def _gp_rest(generator, discriminator, xhat, lambd):
     ops, _, dn = _nets(generator, discriminator)
-    return E.gp_loss_rest(ops, dn, xhat, float(lambd), grad_scale=D_.gp_grad_scale())
+    _amp_latch(ops, discriminator)
+    return _amp_loss(ops, discriminator, E.gp_loss_rest(ops, dn, xhat, float(lambd), grad_scale=D_.gp_grad_scale()))
 
 
 def _g_step(generator, discriminator, optimizer_generator, noise):
@@ -755,12 +786,22 @@ class _Runner:
             tuple(m.flat.gen for m in modules) + \
             tuple((o.buf_gen, float(o.param_groups[0]["lr"]), tuple(float(b) for b in o.param_groups[0]["betas"]),
                    float(o.param_groups[0]["eps"]), float(o.param_groups[0].get("weight_decay", 0.0))) for o in hip_opts)
+        amp = tuple(_amp_key(m) for m in list(modules) + [o._module for o in hip_opts if o._module is not None])
+        if any(a is not None for a in amp):
+            # dynamic loss scaling: which scaler state the launches read (never its value -- that lives on the device)
+            key = key + ("amp",) + amp
         sg = self._graphs.get(key)
         if sg is None:
             while len(self._graphs) >= self.MAX_GRAPHS:          # e.g. one lr value per epoch under a scheduler
                 self._graphs.pop(next(iter(self._graphs)))
             sg = self._graphs[key] = graphed.StepGraph(fn, inputs, modules, hip_opts, stepped)
         return sg
+
+
+def _amp_key(module):
+    ops = getattr(module, "_rt_ops", None)
+    sc = getattr(ops, "amp", None)
+    return None if sc is None else (id(sc), sc.state.data_ptr())
 
 
 _APPLY_RUNNER = _Runner()

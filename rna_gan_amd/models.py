@@ -130,6 +130,8 @@ class _HipModule(nn.Module):
             from .ops_hip import HipOps
             dt = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[self.precision]
             self._rt_ops = D_.attach_sync(HipOps(dt, p0.device))
+            if getattr(self, "_amp_scaler", None) is not None:
+                self._amp_scaler.attach_ops(self._rt_ops)       # rna_gan_amd.amp: the scaler survives a rebuilt backend
             self._rt_net = self._build_net()
             for cw in self._rt_net.convs():
                 cw.owner = "D" if hasattr(self, "disc") else "G"

@@ -136,7 +136,14 @@ class HipOps:
         self.loss_scale = 1.0
         self.gp_seed_scale = 1.0
         self.gp_tangent_scale = 1.0
-        if self.half == "f16":
+        # dynamic loss scaling (rna_gan_amd.amp, opt-in): the seeds read the scale from the device (the exponent latched for
+        # network amp_slot), loss_scale stays 1; None = the static scale above
+        self.amp = None
+        self.amp_slot = 0
+        if self.half == "f16" and os.environ.get("RNAGAN_F16_LOSS_SCALE", "").strip().lower() == "dynamic":
+            from .amp import default_scaler
+            self.amp = default_scaler(self.device)
+        elif self.half == "f16":
             ls = float(os.environ.get("RNAGAN_F16_LOSS_SCALE", "4096"))
             rt = ls ** 0.5
             if ls < 1.0 or rt != int(rt) or (int(rt) & (int(rt) - 1)) != 0:
@@ -900,6 +907,11 @@ class HipOps:
 
     def gp_coef_parts(self, parts, lambd: float):
         loss, coef = self._f32(1), self._f32(1)
+        if self.amp is not None:
+            check(self.lib.rg_gp_coef_parts_scaled_dev(_ptr(parts), parts.shape[0], None, _ptr(loss), _ptr(coef), float(lambd),
+                                                       _ptr(self.amp.state), self.amp_slot, self.stream),
+                  "rg_gp_coef_parts_scaled_dev")
+            return loss, coef
         check(self.lib.rg_gp_coef_parts_scaled(_ptr(parts), parts.shape[0], None, _ptr(loss), _ptr(coef), float(lambd),
                                                float(self.gp_seed_scale), float(self.gp_tangent_scale), self.stream),
               "rg_gp_coef_parts_scaled")
@@ -1043,8 +1055,14 @@ class HipOps:
                                    self.stream), "rg_head_fwd")
         return h, out
 
-    def head_grad(self, h, coef: float, slope: float):
+    def head_grad(self, h, coef: float, slope: float, part: int = 0):
+        """part (dynamic loss scaling only): which power of the latched scale 2^k the seed carries -- 0: 2^k, 1: 2^floor(k/2)
+        (the penalty's first backward; rna_gan_amd.amp).  With the static scale the caller's coef already holds it."""
         gh = torch.empty_like(h)
+        if self.amp is not None:
+            check(self.lib.rg_head_grad_dev(_ptr(h), _ptr(gh), h.numel(), float(coef), _ptr(self.amp.state), self.amp_slot,
+                                            int(part), float(slope), self.stream), "rg_head_grad_dev")
+            return gh
         check(self.lib.rg_head_grad(_ptr(h), _ptr(gh), h.numel(), float(coef), float(slope), self.stream),
               "rg_head_grad")
         return gh
@@ -1368,6 +1386,10 @@ class HipOps:
 
     def gp_coef(self, sq, lambd: float):
         loss, coef = self._f32(1), self._f32(1)
+        if self.amp is not None:
+            check(self.lib.rg_gp_coef_scaled_dev(_ptr(sq), _ptr(loss), _ptr(coef), float(lambd), _ptr(self.amp.state),
+                                                 self.amp_slot, self.stream), "rg_gp_coef_scaled_dev")
+            return loss, coef
         check(self.lib.rg_gp_coef_scaled(_ptr(sq), _ptr(loss), _ptr(coef), float(lambd), float(self.gp_seed_scale),
                                          float(self.gp_tangent_scale), self.stream), "rg_gp_coef_scaled")
         return loss, coef

@@ -86,9 +86,15 @@ class Adam(torch.optim.Adam):
         for p in (self._flat_id.params if self._flat_id is not None else []):
             self.state[p]["step"] = torch.tensor(float(self._host_steps))
 
+    def _amp(self):
+        return getattr(getattr(self._module, "_rt_ops", None), "amp", None) if self._module is not None else None
+
     def state_dict(self):
         from . import dist as D_
         D_.flush()                 # a data-parallel train_op may have left this optimizer's step in flight
+        if self._amp() is not None and self._step_dev is not None:
+            # dynamic loss scaling: skipped steps do not count -- the device counter is the truth, not the host's tally
+            self._host_steps = int(self._step_dev.item())
         self._sync_step_state()
         return super().state_dict()
 
@@ -139,10 +145,23 @@ class Adam(torch.optim.Adam):
         lib = mops.lib if mops is not None else _abi.load()
         ginv = 1.0 / float(getattr(mops, "loss_scale", 1.0)) if mops is not None else 1.0
         stream = torch.cuda.current_stream(flat.data.device).cuda_stream
-        check(lib.rg_adam_hyper_dev2(self._step_dev.data_ptr(), float(g["lr"]), float(g["betas"][0]),
-                                     float(g["betas"][1]), float(g["eps"]), float(g.get("weight_decay", 0.0)), ginv,
-                                     self._hyper.data_ptr(), stream),
-              "rg_adam_hyper_dev2")
+        # dynamic loss scaling (rna_gan_amd.amp): the launches below are collected first, together with the gradient ranges they
+        # read; then probe -> rg_adam_hyper_dev3 (skip word) -> the launches -> the scale update.  Without a scaler: the hyper
+        # launch, then the same launches in the same order as always.
+        amp = getattr(mops, "amp", None) if mops is not None else None
+        launches, probes = [], []
+        if amp is None:
+            check(lib.rg_adam_hyper_dev2(self._step_dev.data_ptr(), float(g["lr"]), float(g["betas"][0]),
+                                         float(g["betas"][1]), float(g["eps"]), float(g.get("weight_decay", 0.0)), ginv,
+                                         self._hyper.data_ptr(), stream),
+                  "rg_adam_hyper_dev2")
+        H16 = getattr(mops, "H16", _abi.RG_BF16)
+
+        def seg(t, n=None, dt=None):
+            # a probe range: a tensor (its dtype names the code) or an address with an explicit count and code
+            if torch.is_tensor(t):
+                return (t.data_ptr(), t.numel() if n is None else n, _abi.RG_F32 if t.dtype == torch.float32 else H16)
+            return (t, n, dt)
         shadow = flat.shadow           # bf16 image of the parameters (bf16 precision only), written by the same launch
         lo = 0
         g0 = getattr(getattr(self._module, "_rt_net", None), "g0", None)
@@ -160,9 +179,11 @@ class Adam(torch.optim.Adam):
             # (data parallel: z / gy are the factors gathered from all ranks, K = world x batch; the rest of the buffer steps
             # from the all-reduced wire below)
             E, C = g0.w.shape[0], g0.w.shape[1]
-            check(lib.rg_g0_wgrad_adam(z.data_ptr(), gy.data_ptr(), flat.data.data_ptr(), self._m.data_ptr(),
-                                       self._v.data_ptr(), self._hyper.data_ptr(), 0 if shadow is None else shadow.data_ptr(),
-                                       z.shape[0], E, C, dt, stream), "rg_g0_wgrad_adam")
+            launches.append(lambda z=z, gy=gy, E=E, C=C, dt=dt: check(lib.rg_g0_wgrad_adam(
+                z.data_ptr(), gy.data_ptr(), flat.data.data_ptr(), self._m.data_ptr(), self._v.data_ptr(),
+                self._hyper.data_ptr(), 0 if shadow is None else shadow.data_ptr(), z.shape[0], E, C, dt, stream),
+                "rg_g0_wgrad_adam"))
+            probes += [seg(z), seg(gy)]
             lo = n0
         # nn.Linear weights whose gradient operands the backward left behind (bind(fuse_linear_wgrad=True)): gradient + Adam
         # in one pass per weight; everything between those segments (biases, BatchNorm parameters) steps from .grad as usual
@@ -180,10 +201,11 @@ class Adam(torch.optim.Adam):
                 # pack: {"image": bf16 [Np][Kp] zero-initialised, "version": ...} -- the runtime's operand image of this weight; the
                 # kernel refreshes it from the updated values, and it is marked current for the tensor version seen here
                 img = None if pack is None else pack["image"]
-                check(lib.rg_linear_wgrad_adam(gT.data_ptr(), xT.data_ptr(), gT.shape[1], nsamp, flat.data.data_ptr() + 4 * off,
-                                               self._m.data_ptr() + 4 * off, self._v.data_ptr() + 4 * off,
-                                               self._hyper.data_ptr(), O_, I_, 0 if img is None else img.data_ptr(),
-                                               0 if img is None else img.shape[1], stream), "rg_linear_wgrad_adam")
+                launches.append(lambda gT=gT, xT=xT, nsamp=nsamp, off=off, O_=O_, I_=I_, img=img: check(lib.rg_linear_wgrad_adam(
+                    gT.data_ptr(), xT.data_ptr(), gT.shape[1], nsamp, flat.data.data_ptr() + 4 * off,
+                    self._m.data_ptr() + 4 * off, self._v.data_ptr() + 4 * off, self._hyper.data_ptr(), O_, I_,
+                    0 if img is None else img.data_ptr(), 0 if img is None else img.shape[1], stream), "rg_linear_wgrad_adam"))
+                probes += [seg(gT), seg(xT)]
                 if pack is not None:
                     pack["version"] = w._version
                 segs.append((off, off + O_ * I_))
@@ -214,16 +236,19 @@ class Adam(torch.optim.Adam):
                     raise RuntimeError("rna_gan_amd.optim.Adam: a deferred single-launch weight gradient expects a bf16 step and "
                                        "a 16-byte aligned tensor inside the flat buffer")
                 ops = getattr(self._module, "_rt_ops", None)
-                call = lambda: check(lib.rg_conv_wgrad_adam(
+                call = lambda low0=low0, high0=high0, low1=low1, high1=high1, off=off, N_=N_, Ho_=Ho_, Wo_=Wo_, O_=O_, I_=I_, \
+                    dt=dt, algo=algo: check(lib.rg_conv_wgrad_adam(
                     low0.data_ptr(), high0.data_ptr(), 0 if low1 is None else low1.data_ptr(),
                     0 if high1 is None else high1.data_ptr(), flat.data.data_ptr() + 4 * off, self._m.data_ptr() + 4 * off,
                     self._v.data_ptr() + 4 * off, self._hyper.data_ptr(), shadow.data_ptr() + 2 * off, N_, Ho_, Wo_, O_, I_, dt,
                     algo, stream), "rg_conv_wgrad_adam")
                 if ops is not None and hasattr(ops, "_timed"):
                     # bench.py's per-family timing: a family of its own -- the launch's interval includes the Adam epilogue
-                    ops._timed("conv_wgrad_adam", flops, call, cw=cw)
+                    launches.append(lambda call=call, flops=flops, cw=cw, ops=ops: ops._timed("conv_wgrad_adam", flops, call, cw=cw))
                 else:
-                    call()
+                    launches.append(call)
+                # (the gradient tile never reaches memory: its operands are probed)
+                probes += [seg(t) for t in (low0, high0, low1, high1) if t is not None]
                 slab_segs.append((off, cw.w.numel(), None, -1, 0))
         if slab_segs:
             if segs or self.grad_wire is not None:
@@ -249,22 +274,37 @@ class Adam(torch.optim.Adam):
             slabs = (C.c_void_p * k)(*[t[2] or None for t in table])
             nsp = (C.c_int * k)(*[t[3] for t in table])
             sdts = (C.c_int * k)(*[t[4] for t in table])
-            check(lib.rg_adam_step_slabs(flat.data.data_ptr() + 4 * lo, flat.grad.data_ptr() + 4 * lo,
-                                         self._m.data_ptr() + 4 * lo, self._v.data_ptr() + 4 * lo, total - lo,
-                                         self._hyper.data_ptr(), 0 if shadow is None else shadow.data_ptr() + 2 * lo, k,
-                                         C.addressof(offs), C.addressof(lens), C.addressof(slabs), C.addressof(nsp),
-                                         C.addressof(sdts), stream),
-                  "rg_adam_step_slabs")
+            launches.append(lambda k=k, offs=offs, lens=lens, slabs=slabs, nsp=nsp, sdts=sdts: check(lib.rg_adam_step_slabs(
+                flat.data.data_ptr() + 4 * lo, flat.grad.data_ptr() + 4 * lo, self._m.data_ptr() + 4 * lo,
+                self._v.data_ptr() + 4 * lo, total - lo, self._hyper.data_ptr(),
+                0 if shadow is None else shadow.data_ptr() + 2 * lo, k, C.addressof(offs), C.addressof(lens),
+                C.addressof(slabs), C.addressof(nsp), C.addressof(sdts), stream), "rg_adam_step_slabs"))
+            for off, n, sp, ns, sdt in table:
+                if sp:                            # the split-K slabs / bias partials the launch sums
+                    probes.append(seg(sp, ns * n, _abi.RG_F32 if sdt == _abi.RG_F32 else H16))
+                elif ns == 0:                     # a range read from .grad (ns = -1: stepped by rg_conv_wgrad_adam, probed above)
+                    probes.append(seg(flat.grad.data_ptr() + 4 * (lo + off), n, _abi.RG_F32))
             segs = [(lo, total)]                  # nothing left for the plain launches below
         pos = lo
+        wire = self.grad_wire
         for a, b in segs + [(flat.data.numel(), flat.data.numel())]:
             if a > pos:
-                check(lib.rg_adam_step_dev(flat.data.data_ptr() + 4 * pos, flat.grad.data_ptr() + 4 * pos,
-                                           self._m.data_ptr() + 4 * pos, self._v.data_ptr() + 4 * pos, a - pos,
-                                           self._hyper.data_ptr(), 0 if shadow is None else shadow.data_ptr() + 2 * pos,
-                                           0 if self.grad_wire is None else self.grad_wire.data_ptr() + 2 * pos, stream),
-                      "rg_adam_step_dev")
+                launches.append(lambda pos=pos, a=a: check(lib.rg_adam_step_dev(
+                    flat.data.data_ptr() + 4 * pos, flat.grad.data_ptr() + 4 * pos, self._m.data_ptr() + 4 * pos,
+                    self._v.data_ptr() + 4 * pos, a - pos, self._hyper.data_ptr(),
+                    0 if shadow is None else shadow.data_ptr() + 2 * pos, 0 if wire is None else wire.data_ptr() + 2 * pos,
+                    stream), "rg_adam_step_dev"))
+                # (data parallel: the all-reduced 16-bit wire, or the fp32 gradient the collective reduced in place)
+                probes.append(seg(flat.grad.data_ptr() + 4 * pos, a - pos, _abi.RG_F32) if wire is None else
+                              seg(wire.data_ptr() + 2 * pos, a - pos, H16))
             pos = max(pos, b)
+        if amp is not None:
+            amp.probe(lib, self._module, probes, stream)
+            amp.hyper(lib, self._module, self._step_dev, g, self._hyper, stream)
+        for fn in launches:
+            fn()
+        if amp is not None:
+            amp.update(lib, self._module, stream)
         if not torch.cuda.is_current_stream_capturing():
             self._host_steps += 1
         self._module.weights_changed(by_optimizer=True)

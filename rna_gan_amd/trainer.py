@@ -34,7 +34,8 @@ from .prefetch import DevicePrefetcher
 class Trainer:
     def __init__(self, models, losses_list, metrics_list=None, device=torch.device("cuda:0"), ncritic=1, epochs=5,
                  sample_size=8, checkpoints="./model/gan", retain_checkpoints=5, recon="./images", log_dir=None,
-                 test_noise=None, nrow=8, precision="bf16", prefetch=True, **kwargs):
+                 test_noise=None, nrow=8, precision="bf16", prefetch=True, loss_scaling="static", loss_scaling_args=None,
+                 **kwargs):
         self.device = torch.device(device)
         self.prefetch = bool(prefetch)          # extra knob: host batches are copied to the device one iteration ahead
         self.pipeline = bool(kwargs.pop("pipeline", True))   # extra knob: see train_iter
@@ -65,6 +66,22 @@ class Trainer:
             mod = getattr(self, m)
             for t in list(mod.parameters()) + list(mod.buffers()):
                 D_.broadcast_(t.data, 0)
+        # loss scaling: "static" (the fp16 build's fixed scale, RNAGAN_F16_LOSS_SCALE) or "dynamic" (rna_gan_amd.amp: GradScaler's
+        # rule on the device with skipped steps; ONE scaler shared by the networks, whose train_ops are seeded through G's backend)
+        if loss_scaling not in ("static", "dynamic"):
+            raise ValueError("loss_scaling must be 'static' or 'dynamic'")
+        self.loss_scaler = None
+        hip_models = [getattr(self, m) for m in self.model_names if hasattr(getattr(self, m), "runtime")]
+        if loss_scaling == "dynamic":
+            from .amp import DynamicLossScaler
+            self.loss_scaler = DynamicLossScaler(**(loss_scaling_args or {}))
+            self.loss_scaler.attach(*hip_models)
+        elif loss_scaling_args:
+            raise ValueError("loss_scaling_args needs loss_scaling='dynamic'")
+        elif precision == "fp16" and os.environ.get("RNAGAN_F16_LOSS_SCALE", "").strip().lower() == "dynamic" and hip_models:
+            # the backends took the process's default scaler (ops_hip.HipOps): the trainer owns it for checkpoints and the log
+            self.loss_scaler = hip_models[0].runtime()[0].amp
+            self.loss_scaler.attach(*hip_models)
         self.losses = {}
         for loss in losses_list:
             self.losses[type(loss).__name__] = loss
@@ -113,6 +130,8 @@ class Trainer:
                  "metric_objects": self.metrics, "loss_logs": self.loss_logs, "metric_logs": self.metric_logs}
         for save_item in self.model_names + self.optimizer_names:
             model.update({save_item: getattr(self, save_item).state_dict()})
+        if self.loss_scaler is not None:
+            model["loss_scaler"] = self.loss_scaler.state_dict()
         if save_items is not None:
             for it in ([save_items] if isinstance(save_items, str) else save_items):
                 model.update({it: getattr(self, it)})
@@ -144,6 +163,8 @@ class Trainer:
             self.metric_logs = checkpoint.get("metric_logs", self.metric_logs)
             for load_item in self.model_names + self.optimizer_names:
                 getattr(self, load_item).load_state_dict(checkpoint[load_item])
+            if self.loss_scaler is not None and "loss_scaler" in checkpoint:
+                self.loss_scaler.load_state_dict(checkpoint["loss_scaler"])
             if load_items is not None:
                 for it in ([load_items] if isinstance(load_items, str) else load_items):
                     obj = checkpoint[it]
@@ -326,6 +347,9 @@ class Trainer:
                 print("Epoch {} Summary\ngenerator Mean Loss : {}\ndiscriminator Mean Loss : {}".format(
                     epoch + 1, self.loss_information["generator_losses"] / gi,
                     self.loss_information["discriminator_losses"] / di))
+                if self.loss_scaler is not None:
+                    st = self.loss_scaler.state_dict()
+                    print("loss scale : {:g}  skipped steps : {}".format(st["scale"], st["skipped_steps"]))
             self.sample_images(epoch)
             for sch in self.schedulers:
                 sch.step()

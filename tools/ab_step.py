@@ -95,6 +95,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--prime", type=int, default=40)
     ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"],
+                    help="precision of every variant's workload (fp16: e.g. an env variant RNAGAN_F16_LOSS_SCALE=dynamic against the "
+                         "static scale)")
     ap.add_argument("--json", default=None, help="write the result object here as well")
     ap.add_argument("--no-control", action="store_true",
                     help="by default the FIRST variant is built a second time (name + '#control', same settings, own buffers) "
@@ -107,7 +110,8 @@ def main():
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     torch.set_num_threads(min(8, torch.get_num_threads()))
-    bargs = bench.parse_args(["--batch", str(a.batch), "--no-cpu-baseline", "--no-roofline", "--no-extras"])
+    bargs = bench.parse_args(["--batch", str(a.batch), "--precision", a.precision, "--no-cpu-baseline", "--no-roofline",
+                              "--no-extras"])
     bargs.prime = a.prime
     pv = parse_variants(a.variants)
     if not a.no_control and pv:
