@@ -11,7 +11,8 @@ Workload = BASELINE.json configs[1] ("RNA-GAN lung 256x256 bf16 batch 64 on 1xMI
 --gpus N it is configs[2] (64 per rank, weak scaling, RCCL gradient all-reduce).
 
 Contract: W untimed warm-up steps, K timed steps bracketed by barrier + synchronize, MAX over
-ranks, rank 0 prints ONE JSON line.  Extra objects:
+ranks, rank 0 prints ONE JSON line.  That, and --dump-outputs, is all a plain run does.  With --full the
+line also carries the objects below, measured after the timed region (about two minutes more):
   roofline     : dominant kernel (bf16 MFMA implicit-GEMM conv, gather_gemm_kernel), achieved =
                  algorithmic conv FLOPs of its launches / their summed duration, measured with
                  HIP events inside this process on a dedicated pass (see DESIGN.md "Measurement").
@@ -120,6 +121,9 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch (BASELINE configs[1])")
     ap.add_argument("--precision", default=os.environ.get("RNAGAN_BENCH_PRECISION", "bf16"), choices=["bf16", "fp32", "fp16"],
                     help="default bf16 (the headline); RNAGAN_BENCH_PRECISION sets the default for launchers that pass no flags")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what the headline figure does not need: roofline (with its "
+                         "on-box ceilings), config.extras, parity and cpu_baseline; the --no-* options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-ceilings", action="store_true", help="skip the on-box ceiling probes (~15 s) of roofline.peak_measured")
@@ -143,6 +147,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_roofline = args.no_ceilings = args.no_cpu_baseline = args.no_extras = True
     if args.gan_type != "dcgan":
         args.no_roofline = args.no_cpu_baseline = args.no_extras = True
     if args.api_path or args.precision != "bf16" or args.batch != 64:

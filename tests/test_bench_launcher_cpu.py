@@ -48,6 +48,24 @@ def test_failing_rank_fails_the_launch():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_plain_run_leaves_the_full_measurements_out(monkeypatch):
+    """Without --full a run does only what its headline figure needs: parse_args turns off every leg main() runs behind the
+    timed region (the roofline pass and its ceilings, the extras and parity, the CPU baseline).  --full turns them on, the
+    --no-* options still leave single legs out of it, and the timed work is configured the same either way."""
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    monkeypatch.delenv("RNAGAN_BENCH_PRECISION", raising=False)
+    import bench
+    legs = ("no_roofline", "no_ceilings", "no_extras", "no_cpu_baseline")
+    argv = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    plain, full = bench.parse_args(argv), bench.parse_args(argv + ["--full"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    assert full.full and not any(getattr(full, k) for k in legs)
+    part = bench.parse_args(argv + ["--full", "--no-extras", "--no-cpu-baseline"])
+    assert [k for k in legs if getattr(part, k)] == ["no_extras", "no_cpu_baseline"]
+    timed = ("gpus", "steps", "warmup", "batch", "precision", "seed", "gan_type", "api_path", "sync_stats", "dump_outputs")
+    assert [getattr(plain, k) for k in timed] == [getattr(full, k) for k in timed]
+
+
 def test_dump_outputs_hold_the_last_timed_step(tmp_path):
     """--dump-outputs DIR: the last timed step's loss values (those of the JSON line) and the trained parameters and buffers
     as float .npy files; two runs with the same arguments write the same arrays, and --steps sets how many steps ran."""

@@ -28,7 +28,8 @@ echo "devices visible: $NDEV (asked for up to $MAXG)"
 if [ "$NDEV" -lt 2 ]; then echo "needs >= 2 GPUs: only the N = 1 line will be produced"; fi
 [ "$MAXG" -gt "$NDEV" ] && MAXG=$NDEV
 PORT=29611
-EXTRA=""; [ "${DP_FIRST_RUN_SELFTEST:-0}" = "1" ] && EXTRA="--no-roofline --no-ceilings"     # (the self-test checks that the lines run, not their fractions)
+# --full: every line reports its roofline figure; the self-test checks that the lines run, not their fractions
+EXTRA="--full"; [ "${DP_FIRST_RUN_SELFTEST:-0}" = "1" ] && EXTRA="--no-roofline --no-ceilings"
 
 run_bench () {   # run_bench N tag [ENV=VAL ...]
   local n=$1 tag=$2; shift 2
