@@ -23,7 +23,7 @@ Gradient penalty without autograd (DESIGN.md "GP second-order pass"):
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -229,7 +229,7 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
     wgrad == "defer": the small parameter gradients (head, BatchNorm, layer-0 bias) are produced now, the conv weight
     gradients are NOT -- their operands gz stay on ctx.gz_keep for a later call with partner=ctx, whose per-layer weight
     gradient is then ONE two-segment launch over both chains (written, whatever ``accumulate`` says for the rest): the
-    data-parallel D-loss step's prefix / rest pair (disc_loss_prefix_dgrad / disc_loss_rest_pairw).
+    data-parallel D-loss step's prefix / rest pair (disc_loss_prefix(backward="dgrad") / disc_loss_rest).
     seed_part: under dynamic loss scaling, the power of the device scale the seed carries (ops.head_grad)."""
     R = len(D.blocks)
     defer_w = isinstance(wgrad, str) and wgrad == "defer"
@@ -604,61 +604,47 @@ def gen_loss_grads(ops, G: GenNet, D: DiscNet, noise, grad_scale: float = 1.0):
     return gen_loss_rest(ops, G, D, gen_loss_prefix(ops, G, noise), grad_scale)
 
 
-def disc_loss_prefix(ops, D: DiscNet, real):
-    """D(real): reads the discriminator only."""
-    return disc_forward(ops, D, real)
+class DiscPrefix(NamedTuple):
+    """What the D-loss step's prefix hands to its rest: D(real), its forward context (None once nothing needs it any more) and
+    which part of D(real)'s backward the prefix already ran (disc_loss_prefix)."""
+    out_r: object
+    ctx_r: object
+    backward: object
 
 
-def disc_loss_prefix_bwd(ops, D: DiscNet, real, grad_scale: float = 1.0):
-    """Data-parallel prefix of the D-loss step: D(real) forward AND its whole backward (the loss is a difference of two
-    means and BatchNorm statistics are per call, so the real half's parameter gradients -mean'(D(real)) do not depend on
-    the generator at all): everything here reads the discriminator only, so the generator's gradient all-reduce of the
-    previous train_op (the largest collective of an iteration) stays in flight under a forward AND a backward pass.
-    Parameter gradients are WRITTEN; disc_loss_rest_acc adds the fake half's."""
+def disc_loss_prefix(ops, D: DiscNet, real, backward=None, grad_scale: float = 1.0):
+    """D(real): reads the discriminator only.  backward: what of D(real)'s backward runs here too -- the loss is a difference
+    of two means and BatchNorm statistics are per call, so the real half's parameter gradients -mean'(D(real)) do not depend
+    on the generator at all; in a data-parallel run the generator's gradient all-reduce of the previous train_op (the largest
+    collective of an iteration) then stays in flight under a forward AND a backward pass.
+      None    nothing: the rest runs both halves' backward chains in lock step (disc_backward_pair);
+      "all"   the whole backward: parameter gradients are WRITTEN, the rest adds the fake half's;
+      "dgrad" the DATA-gradient chain (BatchNorm backward, transposed convs, the small parameter gradients); the conv weight
+              gradients wait for the fake half so that each layer's is one two-segment launch with one split-K reduction in
+              the rest -- the prefix is shorter by those launches (less cover for the generator's all-reduce), the train_op
+              loses five weight-gradient launches and reductions."""
     out_r, ctx_r = disc_forward(ops, D, real)
-    n = out_r.shape[0]
-    disc_backward(ops, D, ctx_r, -grad_scale / n, wgrad=True, accumulate=False, need_input_grad=False)
-    return out_r
+    if backward is not None:
+        n = out_r.shape[0]
+        disc_backward(ops, D, ctx_r, -grad_scale / n, wgrad=True if backward == "all" else "defer", accumulate=False,
+                      need_input_grad=False)
+    return DiscPrefix(out_r, None if backward == "all" else ctx_r, backward)
 
 
-def disc_loss_rest_acc(ops, G, D: DiscNet, out_r, noise, grad_scale: float = 1.0):
-    """The rest of that step: G(z), D(fake), the loss, and the fake half's backward ACCUMULATED onto the real half's."""
-    n = out_r.shape[0]
-    img, _ = _gen_fwd(ops, G, noise, keep=False)
-    out_f, ctx_f = disc_forward(ops, D, img)
-    loss = ops.mean_diff(out_f, out_r, 1.0)
-    disc_backward(ops, D, ctx_f, grad_scale / n, wgrad=True, accumulate=True, need_input_grad=False)
-    return loss
-
-
-def disc_loss_prefix_dgrad(ops, D: DiscNet, real, grad_scale: float = 1.0):
-    """Data-parallel prefix, third form (RNAGAN_DP_PREFIX_BWD=2): D(real) forward and its DATA-gradient chain (BatchNorm
-    backward, transposed convs, the small parameter gradients); the conv weight gradients wait for the fake half so that each
-    layer's is one two-segment launch with one split-K reduction (disc_loss_rest_pairw) -- the prefix is shorter by those
-    launches (less cover for the generator's all-reduce), the train_op loses five weight-gradient launches and reductions."""
-    out_r, ctx_r = disc_forward(ops, D, real)
-    n = out_r.shape[0]
-    disc_backward(ops, D, ctx_r, -grad_scale / n, wgrad="defer", accumulate=False, need_input_grad=False)
-    return out_r, ctx_r
-
-
-def disc_loss_rest_pairw(ops, G, D: DiscNet, pre, noise, grad_scale: float = 1.0):
-    out_r, ctx_r = pre
+def disc_loss_rest(ops, G, D: DiscNet, pre: DiscPrefix, noise, grad_scale: float = 1.0):
+    """The rest of that step: G(z), D(fake), the loss, and whatever of the backward the prefix left (pre.backward): both
+    halves in lock step, or the fake half's ACCUMULATED onto the real half's -- with the conv weight gradients of both halves
+    paired up here when the prefix ran the data-gradient chain only."""
+    out_r, ctx_r, backward = pre
     n = out_r.shape[0]
     img, _ = _gen_fwd(ops, G, noise, keep=False)
     out_f, ctx_f = disc_forward(ops, D, img)
     loss = ops.mean_diff(out_f, out_r, 1.0)
-    disc_backward(ops, D, ctx_f, grad_scale / n, wgrad=True, accumulate=True, need_input_grad=False, partner=ctx_r)
-    return loss
-
-
-def disc_loss_rest(ops, G, D: DiscNet, pre, noise, grad_scale: float = 1.0):
-    out_r, ctx_r = pre
-    n = out_r.shape[0]
-    img, _ = _gen_fwd(ops, G, noise, keep=False)
-    out_f, ctx_f = disc_forward(ops, D, img)
-    loss = ops.mean_diff(out_f, out_r, 1.0)
-    disc_backward_pair(ops, D, ctx_r, -grad_scale / n, ctx_f, grad_scale / n)
+    if backward is None:
+        disc_backward_pair(ops, D, ctx_r, -grad_scale / n, ctx_f, grad_scale / n)
+    else:
+        disc_backward(ops, D, ctx_f, grad_scale / n, wgrad=True, accumulate=True, need_input_grad=False,
+                      partner=ctx_r if backward == "dgrad" else None)
     return loss
 
 

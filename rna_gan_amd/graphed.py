@@ -63,6 +63,7 @@ class StepGraph:
         self.calls = 0
         self.failed = False
         self._out_spec = None          # (shape, dtype, device) of every tensor the last eager run returned
+        self.wire_cell = None          # data parallel: what fn's last eager run recorded for the all-reduce (losses._Runner._dp_grads)
         self._rebuilt = {}             # fp32-storage modules: {id(module): [ConvW whose operand images the captured function rebuilds]}
 
     STABLE_NUMEL = 4096                # outputs up to this size get a home outside the graph pool

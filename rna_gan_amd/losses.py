@@ -16,6 +16,7 @@ computed; in a data-parallel run the flat gradient buffer is all-reduced before 
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -140,7 +141,7 @@ def _nets(generator, discriminator):
     od, dn = discriminator.runtime()
     if og.act_dtype != od.act_dtype:
         raise RuntimeError("generator and discriminator must use the same precision")
-    if getattr(og, "amp", None) is not getattr(od, "amp", None):
+    if og.amp is not od.amp:
         # every seed is issued through the generator's backend and every optimizer unscales with its own network's: a scaler on
         # one of them only would leave the other network's gradients off by the scale
         raise RuntimeError("dynamic loss scaling: attach ONE DynamicLossScaler to both the generator and the discriminator "
@@ -160,6 +161,32 @@ def _wire_kind(ops):
     return ops.half
 
 
+def _local_half_dcgan(ops, net):
+    """16-bit kernels on a DCGAN GenNet / DiscNet whose BatchNorm statistics are rank-local: what every deferred weight-gradient
+    form below needs."""
+    return _is_half(ops) and isinstance(net, (E.GenNet, E.DiscNet)) and ops.stat_reduce is None
+
+
+def _is_adam(optimizer):
+    """rna_gan_amd.optim.Adam (the only optimizer with note_replayed / grad_wire), without importing it here."""
+    return hasattr(optimizer, "note_replayed")
+
+
+def _own_adam(stepped, optimizer):
+    """The optimizer is rna_gan_amd.optim.Adam bound to the stepped module (Adam.bind): it consumes what a gradient pass defers."""
+    return _is_adam(optimizer) and optimizer._module is stepped
+
+
+def _grad_scale(ops):
+    """Seed scale of the D / G loss: the data-parallel mean over ranks times the (static) fp16 loss scale."""
+    return D_.grad_scale() * ops.loss_scale
+
+
+def _f32(x):
+    """A step input as the kernels take it."""
+    return x.contiguous().float()
+
+
 def _finish(module, optimizer):
     """all-reduce (data parallel) -> optimizer step -> invalidate packed weights."""
     _reduce(module)
@@ -173,12 +200,12 @@ def _reduce(module):
 
 def _apply(module, optimizer):
     ops, _ = module.runtime()
-    if (ops.loss_scale != 1.0 or getattr(ops, "amp", None) is not None) and getattr(optimizer, "_module", None) is not module:
+    if (ops.loss_scale != 1.0 or ops.amp is not None) and not _own_adam(module, optimizer):
         # fp16: the gradients in module.flat.grad carry the loss scale; only rna_gan_amd.optim.Adam bound to the module unscales
         raise RuntimeError("fp16 precision needs rna_gan_amd.optim.Adam(...).bind(module): a foreign optimizer would step on "
                            "loss-scaled gradients")
     optimizer.step()
-    if not hasattr(optimizer, "note_replayed"):      # rna_gan_amd.optim.Adam reports the change itself
+    if not _is_adam(optimizer):      # rna_gan_amd.optim.Adam reports the change itself
         module.weights_changed()
     return module.flat.data[:1]          # a tensor result, so that this half can be a graph of its own
 
@@ -189,13 +216,13 @@ def _apply(module, optimizer):
 # its latch) is always applied before that network's next train_op seeds: the D step's pending update runs in the flush between
 # the penalty step's prefix (which reads G and seeds nothing) and its rest, G's between the D-loss prefix and rest.
 def _amp_latch(ops, stepped):
-    if getattr(ops, "amp", None) is not None:
+    if ops.amp is not None:
         ops.amp.latch(ops, stepped)
 
 
 def _amp_loss(ops, stepped, loss):
     # (data parallel: the loss is rank-local, so only the all-reduced gradients decide -- every rank decides alike)
-    if getattr(ops, "amp", None) is not None and not D_.active():
+    if ops.amp is not None and not D_.active():
         ops.amp.probe_loss(ops, stepped, loss[0] if isinstance(loss, tuple) else loss)
     return loss
 
@@ -208,21 +235,21 @@ def _amp_loss(ops, stepped, loss):
 # while the prefix runs (run_dp below).
 def _g_prefix(generator, discriminator, noise):
     ops, gn, _ = _nets(generator, discriminator)
-    return E.gen_loss_prefix(ops, gn, noise.contiguous().float())
+    return E.gen_loss_prefix(ops, gn, _f32(noise))
 
 
 def _g_rest(generator, discriminator, pre):
     ops, gn, dn = _nets(generator, discriminator)
     _amp_latch(ops, generator)
-    return _amp_loss(ops, generator, E.gen_loss_rest(ops, gn, dn, pre, grad_scale=D_.grad_scale() * ops.loss_scale))
+    return _amp_loss(ops, generator, E.gen_loss_rest(ops, gn, dn, pre, grad_scale=_grad_scale(ops)))
 
 
 # data-parallel D-loss step: D(real)'s backward belongs to the prefix too (it reads the discriminator only), so the generator's
 # gradient all-reduce -- started by the G-loss step just before -- is covered by a forward and a backward pass
 # (RNAGAN_DP_PREFIX_BWD=0: forward only, as in round 2)
 # RNAGAN_DP_PREFIX_BWD=2 (default since round 4): forward + data-gradient chain in the prefix, the conv weight gradients of
-# both halves as two-segment launches in the rest -- engine.disc_loss_prefix_dgrad.  One rank, same box, interleaved: 12.07 ms
-# against 12.21 ms for mode 1 (single-process path 11.24-11.39); the prefix shrinks from ~1.3 to ~0.9 ms, still longer than the
+# both halves as two-segment launches in the rest -- engine.disc_loss_prefix(backward="dgrad").  One rank, same box,
+# interleaved: 12.07 ms against 12.21 ms for mode 1 (single-process path 11.24-11.39); the prefix shrinks from ~1.3 to ~0.9 ms, still longer than the
 # generator's 90 MB collective at any plausible bus bandwidth.  1: the whole backward of the real half in the prefix (round 3).
 # PROVISIONAL default: the only evidence is a one-rank timing and a world-2 run over gloo on a shared GPU; mode 2's shorter
 # prefix gives the generator's collective less cover, and tools/dp_first_run.sh A/Bs mode 1 on the first real multi-GPU node.
@@ -253,15 +280,12 @@ def _d_prefix(generator, discriminator, real, noise, clip):
     if clip is not None:
         ops.clamp_(discriminator.flat.data, clip[0], clip[1])      # every D parameter (wgan_loss.py:213-215)
         discriminator.weights_changed()
-    if DP_PREFIX_BWD and D_.active():
+    backward = None
+    if D_.active():
+        backward = "dgrad" if DP_PREFIX_MODE == 2 else "all" if DP_PREFIX_BWD else None
+    if backward is not None:
         _amp_latch(ops, discriminator)           # D(real)'s backward is seeded here
-    if DP_PREFIX_MODE == 2 and D_.active():
-        return ("dgrad", E.disc_loss_prefix_dgrad(ops, dn, real.contiguous().float(), grad_scale=D_.grad_scale() * ops.loss_scale)), \
-            noise.contiguous().float()
-    if DP_PREFIX_BWD and D_.active():
-        return ("bwd", E.disc_loss_prefix_bwd(ops, dn, real.contiguous().float(), grad_scale=D_.grad_scale() * ops.loss_scale)), \
-            noise.contiguous().float()
-    return E.disc_loss_prefix(ops, dn, real.contiguous().float()), noise.contiguous().float()
+    return E.disc_loss_prefix(ops, dn, _f32(real), backward, grad_scale=_grad_scale(ops)), _f32(noise)
 
 
 def _d_batched(generator, discriminator, real, noise, clip, next_noise=None):
@@ -273,8 +297,8 @@ def _d_batched(generator, discriminator, real, noise, clip, next_noise=None):
         discriminator.weights_changed()
     _amp_latch(ops, discriminator)
     return _amp_loss(ops, discriminator, E.disc_loss_grads_batched(
-        ops, gn, dn, real.contiguous().float(), noise.contiguous().float(), grad_scale=D_.grad_scale() * ops.loss_scale,
-        next_noise=None if next_noise is None else next_noise.contiguous().float()))
+        ops, gn, dn, _f32(real), _f32(noise), grad_scale=_grad_scale(ops),
+        next_noise=None if next_noise is None else _f32(next_noise)))
 
 
 class _FakeCache:
@@ -284,6 +308,9 @@ class _FakeCache:
     unchanged in between."""
 
     def __init__(self):
+        self.clear()
+
+    def clear(self):
         self.key, self.src, self.img = None, None, None
 
     @staticmethod
@@ -298,7 +325,7 @@ class _FakeCache:
         if self.key is None or self.key != self.make_key(generator, noise_tensors):
             return None
         img = self.img
-        self.key, self.src, self.img = None, None, None
+        self.clear()
         return img
 
 
@@ -328,27 +355,21 @@ def _gp_fake_body(generator, discriminator, lambd):
     """penalty step on a fake batch that is already there: inputs (real, fake, eps)"""
     def prefix(real, fake, eps):
         ops, _, _ = _nets(generator, discriminator)
-        return E.gp_loss_prefix_fake(ops, real.contiguous().float(), fake, eps if torch.is_tensor(eps) else float(eps))
+        return E.gp_loss_prefix_fake(ops, _f32(real), fake, eps if torch.is_tensor(eps) else float(eps))
     return _Body(prefix, lambda xhat: _gp_rest(generator, discriminator, xhat, lambd), generator)
 
 
 def _d_rest(generator, discriminator, pre):
     ops, gn, dn = _nets(generator, discriminator)
-    fwd_real, noise = pre
-    if isinstance(fwd_real, tuple) and fwd_real[0] == "bwd":       # the real half's backward ran in the prefix
-        return _amp_loss(ops, discriminator, E.disc_loss_rest_acc(ops, gn, dn, fwd_real[1], noise,
-                                                                  grad_scale=D_.grad_scale() * ops.loss_scale))
-    if isinstance(fwd_real, tuple) and fwd_real[0] == "dgrad":     # ... its data-gradient chain did; weight gradients pair up here
-        return _amp_loss(ops, discriminator, E.disc_loss_rest_pairw(ops, gn, dn, fwd_real[1], noise,
-                                                                    grad_scale=D_.grad_scale() * ops.loss_scale))
-    _amp_latch(ops, discriminator)
-    return _amp_loss(ops, discriminator, E.disc_loss_rest(ops, gn, dn, fwd_real, noise,
-                                                          grad_scale=D_.grad_scale() * ops.loss_scale))
+    d_real, noise = pre
+    if d_real.backward is None:                  # (else the prefix seeded D(real)'s backward: latched there)
+        _amp_latch(ops, discriminator)
+    return _amp_loss(ops, discriminator, E.disc_loss_rest(ops, gn, dn, d_real, noise, grad_scale=_grad_scale(ops)))
 
 
 def _gp_prefix(generator, discriminator, real, noise, eps):
     ops, gn, _ = _nets(generator, discriminator)
-    return E.gp_loss_prefix(ops, gn, real.contiguous().float(), noise.contiguous().float(),
+    return E.gp_loss_prefix(ops, gn, _f32(real), _f32(noise),
                             eps if torch.is_tensor(eps) else float(eps))
 
 
@@ -421,42 +442,57 @@ def _dispatch(runner, key, body, inputs, generator, discriminator, stepped, opti
         return runner.run_dp(key, body, inputs, mods, stepped, optimizer)
 
     def full(*a):
-        g0 = _fusable_g0(stepped, optimizer)
-        if g0 is not None:
-            g0.fuse_step = True          # this gradient pass is followed at once by optimizer.step(): see ConvW.fuse_step
-        deferred = _slab_layers(stepped, optimizer)
-        for cw in deferred:
-            cw.defer_slabs = True        # ... and the split-K weight gradients of its 4 x 4 layers may stay unreduced slabs
         sk = _skinny_slab_layer(stepped, optimizer)
-        ops_s = generator.runtime()[0] if sk is not None else None      # the HipOps the engine runs BOTH networks on (_nets)
-        # nothing deferred may be left over from an earlier pass that raised before its optimizer step consumed it (a stale
-        # pending_wgrad would also keep that pass's operand activations alive)
-        _drop_deferred(deferred, sk, g0)
-        if sk is not None:
-            ops_s._skinny_defer = {sk.dw.data_ptr(): sk}      # ... and the image-side layer's per-workgroup partials too
-        try:
+        # this gradient pass is followed at once by optimizer.step() (_finish), which consumes what it leaves pending: the split-K
+        # weight gradients of the 4 x 4 layers as unreduced slabs, the image-side layer's per-workgroup partials (registered on
+        # the HipOps the engine runs BOTH networks on, _nets), G.0's operands
+        with _armed(slabs=_slab_layers(stepped, optimizer), skinny=None if sk is None else (generator.runtime()[0], sk),
+                    g0=_fusable_g0(stepped, optimizer)):
             loss = body.grads(*a)
-        except BaseException:
-            _drop_deferred(deferred, sk, g0)     # the step below does not run: the next train_op starts clean
-            raise
-        finally:
-            if g0 is not None:
-                g0.fuse_step = False
-            for cw in deferred:
-                cw.defer_slabs = False
-            if sk is not None:
-                ops_s._skinny_defer = None
         _finish(stepped, optimizer)
         return loss
     return runner.run(key, full, inputs, mods, [optimizer])
 
 
-def _drop_deferred(deferred, sk, g0):
-    """Forget what a gradient pass left for an optimizer step that will not consume it (see _dispatch.full)."""
-    for cw in list(deferred) + [c for c in (sk, g0) if c is not None]:
-        cw.pending_slabs = None
-        cw.pending_bias = None
-        cw.pending_wgrad = None
+@contextlib.contextmanager
+def _armed(slabs=(), wired=(), skinny=None, g0=None, factor_stage=None):
+    """Arm ONE gradient pass to leave weight gradients unreduced for whoever consumes them right after it, and disarm it again.
+      slabs         ConvW handles whose split-K slabs may stay unreduced (ConvW.defer_slabs);
+      wired         data parallel: (ConvW, wire slice) pairs -- defer_slabs plus ConvW.wire_slot;
+      skinny        (HipOps, ConvW): the image-side layer whose per-workgroup partials may stay (HipOps._skinny_defer);
+      g0            generator layer 0's handle: its operands stay on the handle (ConvW.fuse_step), or are copied into this rank's
+                    factor_stage = (z slot, gz0 slot) of the gathered factor buffers (ConvW.factor_stage).
+    On entry nothing may be pending on these layers from an earlier pass that raised before its consumer ran (a stale
+    pending_wgrad would also keep that pass's operand activations alive): dropped.  On exit every flag set here is cleared --
+    a stale one is silent: a later eager pass would leave a gradient unreduced and the optimizer would step without it.  When the
+    body raises, what it left pending is dropped too: no consumer will run, the next train_op starts clean.
+    What is pending after a NORMAL exit is the caller's to consume, and the callers differ: a single process hands it to
+    optimizer.step() (_dispatch: _finish right after the with); a data-parallel pass turns pending_slabs into the all-reduce's
+    segment table and checks / clears g0.pending_wgrad == "staged" before it leaves the with (_dp_armed)."""
+    layers = list(slabs) + [cw for cw, _ in wired] + [c for c in (skinny and skinny[1], g0) if c is not None]
+
+    def drop():
+        for cw in layers:
+            cw.pending_slabs = cw.pending_bias = cw.pending_wgrad = None
+    drop()
+    for cw in slabs:
+        cw.defer_slabs = True
+    for cw, slot in wired:
+        cw.defer_slabs, cw.wire_slot = True, slot
+    if skinny is not None:
+        skinny[0]._skinny_defer = {skinny[1].dw.data_ptr(): skinny[1]}
+    if g0 is not None:
+        g0.fuse_step, g0.factor_stage = True, factor_stage
+    try:
+        yield
+    except BaseException:
+        drop()
+        raise
+    finally:
+        for cw in layers:
+            cw.defer_slabs, cw.wire_slot, cw.fuse_step, cw.factor_stage = False, None, False, None
+        if skinny is not None:
+            skinny[0]._skinny_defer = None
 
 
 # split-K weight-gradient slabs summed inside the optimizer step instead of by a reduction launch per layer (single process,
@@ -465,13 +501,10 @@ SLAB_ADAM = os.environ.get("RNAGAN_SLAB_ADAM", "1") != "0"
 
 
 def _slab_layers(stepped, optimizer):
-    if (not SLAB_ADAM or D_.active() or not hasattr(optimizer, "note_replayed") or
-            getattr(optimizer, "_module", None) is not stepped):
+    if not SLAB_ADAM or D_.active() or not _own_adam(stepped, optimizer):
         return []
     ops, net = stepped.runtime()
-    if not _is_half(ops) or not isinstance(net, (E.GenNet, E.DiscNet)) or ops.stat_reduce is not None:
-        return []
-    return [b[0] for b in net.blocks]
+    return [b[0] for b in net.blocks] if _local_half_dcgan(ops, net) else []
 
 
 SKINNY_SLAB_ADAM = os.environ.get("RNAGAN_SKINNY_SLAB_ADAM", "1") != "0"
@@ -497,16 +530,18 @@ def _skinny_slab_layer(stepped, optimizer):
 G0_ADAM = os.environ.get("RNAGAN_G0_ADAM", "1") != "0"
 
 
-def _fusable_g0(stepped, optimizer):
-    """The stepped module's layer-0 weight handle if its gradient may be formed inside the fused optimizer step: the
-    generator (DCGAN recipe), stepped by rna_gan_amd.optim.Adam bound to it, bf16 kernels, single process."""
-    if not G0_ADAM or D_.active() or not hasattr(optimizer, "note_replayed") or getattr(optimizer, "_module", None) is not stepped:
+def _adam_g0(stepped, optimizer):
+    """The stepped module's layer-0 weight handle if rna_gan_amd.optim.Adam may form its gradient inside the fused step: the
+    generator (DCGAN recipe), stepped by that optimizer bound to it, bf16 kernels."""
+    if not G0_ADAM or not _own_adam(stepped, optimizer):
         return None
     ops, net = stepped.runtime()
-    g0 = getattr(net, "g0", None)
-    if g0 is None or not isinstance(net, E.GenNet) or not _is_half(ops):
-        return None
-    return g0
+    return net.g0 if isinstance(net, E.GenNet) and _is_half(ops) else None
+
+
+def _fusable_g0(stepped, optimizer):
+    """Single process: the optimizer step that follows the pass forms the gradient from the operands left on the handle."""
+    return None if D_.active() else _adam_g0(stepped, optimizer)
 
 
 # D-loss step of a single process: D(real) and D(fake) as one double batch (RNAGAN_D_BATCHED=0: two forward / backward chains)
@@ -534,10 +569,10 @@ def _dp_wire_layers(stepped, optimizer):
     if not (DP_WIRE_DIRECT and SLAB_ADAM and D_.active() and FUSED_WIDEN and (DP_PREFIX_MODE == 2 or DP_ROUTE == "whole")) \
             or D_.sync_stats():
         return []
-    if not hasattr(optimizer, "grad_wire") or getattr(optimizer, "_module", None) is not stepped:
+    if not _own_adam(stepped, optimizer):
         return []
     ops, net = stepped.runtime()
-    if not _wire_kind(ops) or not isinstance(net, (E.GenNet, E.DiscNet)) or ops.stat_reduce is not None:
+    if not _wire_kind(ops) or not _local_half_dcgan(ops, net):
         return []
     flat = stepped.flat
     wire = D_.wire_for(flat.grad, ops.half)
@@ -582,20 +617,45 @@ def _dp_factor_g0(stepped, optimizer, batch):
     """Data parallel: (g0 handle, gathered-factor buffers) when the stepped module's layer-0 weight gradient can travel as
     FACTORS (dist.G0_FACTORS): DCGAN generator stepped by rna_gan_amd.optim.Adam bound to it, bf16 kernels, rank-local
     statistics, and the fused kernel takes K = world x batch."""
-    if not (D_.G0_FACTORS and G0_ADAM and D_.active()) or D_.sync_stats():
+    if not (D_.G0_FACTORS and D_.active()) or D_.sync_stats():
         return None
-    if not hasattr(optimizer, "note_replayed") or getattr(optimizer, "_module", None) is not stepped:
+    g0 = _adam_g0(stepped, optimizer)
+    if g0 is None:
         return None
-    ops, net = stepped.runtime()
-    g0 = getattr(net, "g0", None)
-    if g0 is None or not isinstance(net, E.GenNet) or not _is_half(ops):
-        return None
+    ops, _ = stepped.runtime()
     En, C = g0.w.shape[0], g0.w.shape[1]
     if (g0.w.data_ptr() - stepped.flat.data.data_ptr()) != 0:
         return None
     if not ops.lib.rg_g0_wgrad_adam_supported(D_.world_size() * batch, En, C, ops.dt):
         return None
     return g0, D_.factor_buffers(id(stepped), batch, En, C, ops.h16, stepped.flat.data.device), ops.dt
+
+
+def _dp_plan(stepped, optimizer, inputs):
+    """(fac, wired, head) of a data-parallel gradient pass.  fac: generator-loss step -- layer 0's weight gradient travels as
+    gathered factors (dist.G0_FACTORS): the backward copies z / gz0 into this rank's slices of the gathered buffers instead
+    of forming the 67 M-element product (_dp_factor_g0: None for anything but the generator); wired: _dp_wire_layers;
+    head: the leading elements of the flat gradient that stay off the all-reduce wire (G.0's, when it travels as factors)."""
+    fac = _dp_factor_g0(stepped, optimizer, inputs[0].shape[0]) if inputs else None
+    return fac, _dp_wire_layers(stepped, optimizer), fac[0].w.numel() if fac is not None else 0
+
+
+def _dp_armed(fn, stepped, fac, wired, head, cell):
+    """fn as a data-parallel gradient pass: armed for (fac, wired) of _dp_plan, and what the pass left pending consumed."""
+    g0 = fac[0] if fac is not None else None
+
+    def armed(*a):
+        with _armed(wired=wired, g0=g0, factor_stage=None if fac is None else (fac[1][2], fac[1][3])):
+            out = fn(*a)
+            # what the weight-gradient launches of this pass left: kept with the graph this call captures (a replay runs
+            # no host code, its launches are these)
+            cell["wire_table"] = _dp_wire_table(stepped, wired, head)
+            if g0 is not None:
+                if g0.pending_wgrad != "staged":
+                    raise RuntimeError("data-parallel G step: layer 0's weight gradient was not left as factors")
+                g0.pending_wgrad = None               # (flush hands the GATHERED factors to the optimizer)
+        return out
+    return armed
 
 
 def flush():
@@ -606,7 +666,7 @@ def flush():
         return
     # rna_gan_amd.optim.Adam steps straight from the all-reduced bf16 wire buffer (no widening pass; .grad then keeps
     # the rank-local gradient); other optimizers get the averaged gradient back in .grad first
-    wire = D_.wire_of(pend.handle) if FUSED_WIDEN and hasattr(pend.optimizer, "grad_wire") else None
+    wire = D_.wire_of(pend.handle) if FUSED_WIDEN and _is_adam(pend.optimizer) else None
     # (with gathered G.0 factors the handle's head is excluded from the wire; the tail is widened like any other gradient
     # when the optimizer does not step from the wire -- RNAGAN_DP_FUSED_WIDEN=0 or a foreign optimizer)
     D_.allreduce_finish(pend.handle, widen=wire is None)
@@ -617,7 +677,7 @@ def flush():
             if w is not None:
                 w.wait()
         g0.pending_wgrad = (z_all, gy_all, dt)     # every rank's samples: the fused step forms sum_r z_r^T gz0_r itself
-    if hasattr(pend.optimizer, "grad_wire"):
+    if _is_adam(pend.optimizer):
         pend.optimizer.grad_wire = wire
     try:
         _APPLY_RUNNER.run(("apply", id(pend.module), wire is not None, fac is not None),
@@ -625,7 +685,7 @@ def flush():
     finally:
         if fac is not None:
             fac[0].pending_wgrad = None
-    if hasattr(pend.optimizer, "grad_wire"):
+    if _is_adam(pend.optimizer):
         pend.optimizer.grad_wire = None
 
 
@@ -663,56 +723,8 @@ class _Runner:
         # captured, so the rest graph is tied to that prefix graph and may only be captured after it
         holder = self._pre.setdefault((key, id(sg_pre)), {})
         holder["pre"] = pre
-        # generator-loss step: layer 0's weight gradient travels as gathered factors (dist.G0_FACTORS): the backward copies
-        # z / gz0 into this rank's slices of the gathered buffers instead of forming the 67 M-element product
-        fac = _dp_factor_g0(stepped, optimizer, inputs[0].shape[0]) if stepped is body.prefix_reads and inputs else None
-
-        wired = _dp_wire_layers(stepped, optimizer)
-        head = fac[0].w.numel() if fac is not None else 0
-        # the wire segment table describes the launches of ONE rest graph: it lives with the StepGraph whose function wrote it
-        # (sg_rest.wire_cell below), not in a holder that every variant under this prefix (packs_stale, lr, buf_gen) overwrites
-        cell = {}
-
-        def rest_body():
-            for cw, slot in wired:
-                cw.defer_slabs, cw.wire_slot, cw.pending_slabs = True, slot, None
-            try:
-                out = body.rest(holder["pre"])
-                # what the weight-gradient launches of this pass left: kept with the graph this call captures (a replay runs
-                # no host code, its launches are these)
-                cell["wire_table"] = _dp_wire_table(stepped, wired, head)
-                return out
-            finally:
-                for cw, _ in wired:
-                    cw.defer_slabs, cw.wire_slot, cw.pending_slabs = False, None, None
-
-        def rest():
-            if fac is None:
-                return rest_body()
-            g0, bufs = fac[0], fac[1]
-            g0.fuse_step, g0.factor_stage = True, (bufs[2], bufs[3])
-            try:
-                out = rest_body()
-                if g0.pending_wgrad != "staged":
-                    raise RuntimeError("data-parallel G step: layer 0's weight gradient was not left as factors")
-                return out
-            finally:
-                g0.fuse_step, g0.factor_stage, g0.pending_wgrad = False, None, None
-        sg_rest = self._step_graph(key + ("rest", id(sg_pre), fac is not None, len(wired)), rest, [], modules, [], [])
-        if sg_rest is not None:
-            if getattr(sg_rest, "wire_cell", None) is None:
-                sg_rest.wire_cell = cell              # created by this call: its function is the closure over this cell
-            cell = sg_rest.wire_cell                  # (an existing graph runs / replays the closure of the call that created it)
-            loss = sg_rest(allow_capture=sg_pre is not None and sg_pre.graph is not None)
-        else:
-            loss = rest()
-        ops, _ = stepped.runtime()
-        handle = D_.allreduce_start(stepped.flat.grad, compress=_wire_kind(ops), head=head,
-                                    table=cell.get("wire_table") if wired else None)
-        if fac is not None:
-            z_all, gy_all, z_mine, gy_mine = fac[1]
-            fac = fac + ([D_.allgather_start(z_all, z_mine), D_.allgather_start(gy_all, gy_mine)],)
-        _PENDING[0] = _Pending(stepped, optimizer, handle, fac)
+        loss = self._dp_grads(key + ("rest", id(sg_pre)), lambda: body.rest(holder["pre"]), [], inputs, modules, stepped,
+                              optimizer, allow_capture=sg_pre is not None and sg_pre.graph is not None)
         if not OVERLAP:
             flush()
         return loss
@@ -720,44 +732,34 @@ class _Runner:
     def _run_dp_whole(self, key, body, inputs, modules, stepped, optimizer):
         """Route "whole" (DP_ROUTE): graph(the single process's gradient body) -> all-reduce -> wait -> graph(optimizer step)."""
         flush()
-        _, net = stepped.runtime()
-        fac = _dp_factor_g0(stepped, optimizer, inputs[0].shape[0]) if isinstance(net, E.GenNet) and inputs else None
-        wired = _dp_wire_layers(stepped, optimizer)
-        head = fac[0].w.numel() if fac is not None else 0
-        cell = {}
+        loss = self._dp_grads(key + ("whole",), body.grads, inputs, inputs, modules, stepped, optimizer)
+        flush()                                   # nothing to overlap with: wait and apply now
+        return loss
 
-        def grads(*a):
-            for cw, slot in wired:
-                cw.defer_slabs, cw.wire_slot, cw.pending_slabs = True, slot, None
-            if fac is not None:
-                fac[0].fuse_step, fac[0].factor_stage = True, (fac[1][2], fac[1][3])
-            try:
-                out = body.grads(*a)
-                cell["wire_table"] = _dp_wire_table(stepped, wired, head)
-                if fac is not None and fac[0].pending_wgrad != "staged":
-                    raise RuntimeError("data-parallel G step: layer 0's weight gradient was not left as factors")
-                return out
-            finally:
-                for cw, _ in wired:
-                    cw.defer_slabs, cw.wire_slot, cw.pending_slabs = False, None, None
-                if fac is not None:
-                    fac[0].fuse_step, fac[0].factor_stage, fac[0].pending_wgrad = False, None, None
-        sg = self._step_graph(key + ("whole", fac is not None, len(wired)), grads, inputs, modules, [], [])
+    def _dp_grads(self, key, fn, fn_inputs, step_inputs, modules, stepped, optimizer, allow_capture=True):
+        """What both data-parallel routes do with the gradient part ``fn(*fn_inputs)`` of a train_op: run it armed (_dp_armed) as
+        one graph, START the gradient all-reduce (and the all-gathers of G.0's factors) and leave the optimizer step pending
+        for flush().  step_inputs: the train_op's own inputs (their leading dimension is the batch).  Returns the loss."""
+        fac, wired, head = _dp_plan(stepped, optimizer, step_inputs)
+        # the wire segment table describes the launches of ONE graph: it lives with the StepGraph whose function wrote it
+        # (StepGraph.wire_cell), not in a holder that every variant under one prefix (packs_stale, lr, buf_gen) overwrites
+        cell = {}
+        armed = _dp_armed(fn, stepped, fac, wired, head, cell)
+        sg = self._step_graph(key + (fac is not None, len(wired)), armed, fn_inputs, modules, [], [])
         if sg is not None:
-            if getattr(sg, "wire_cell", None) is None:
-                sg.wire_cell = cell
-            cell = sg.wire_cell
-            loss = sg(*inputs)
+            if sg.wire_cell is None:
+                sg.wire_cell = cell                   # created by this call: its function is the closure over this cell
+            cell = sg.wire_cell                       # (an existing graph runs / replays the closure of the call that created it)
+            loss = sg(*fn_inputs, allow_capture=allow_capture)
         else:
-            loss = grads(*inputs)
+            loss = armed(*fn_inputs)
         ops, _ = stepped.runtime()
         handle = D_.allreduce_start(stepped.flat.grad, compress=_wire_kind(ops), head=head,
                                     table=cell.get("wire_table") if wired else None)
         if fac is not None:
             z_all, gy_all, z_mine, gy_mine = fac[1]
-            fac = fac + ([D_.allgather_start(z_all, z_mine), D_.allgather_start(gy_all, gy_mine)],)
+            fac = fac + ([D_.allgather_start(z, mine) for z, mine in ((z_all, z_mine), (gy_all, gy_mine))],)
         _PENDING[0] = _Pending(stepped, optimizer, handle, fac)
-        flush()                                   # nothing to overlap with: wait and apply now
         return loss
 
     def run(self, key, fn, inputs, modules, optimizers, stepped=None):
@@ -771,7 +773,7 @@ class _Runner:
             return None
         if stepped is None:
             stepped = [o._module for o in optimizers if getattr(o, "_module", None) is not None]
-        hip_opts = [o for o in optimizers if hasattr(o, "note_replayed")]
+        hip_opts = [o for o in optimizers if _is_adam(o)]
         if len(hip_opts) != len(optimizers):
             return None                     # a foreign optimizer keeps host-side state: no capture
         for o in hip_opts:
@@ -934,7 +936,7 @@ LATENT_CACHE = os.environ.get("RNAGAN_LATENT_CACHE", "1") != "0"
 
 def _drop_lookahead():
     _NEXT_NOISE[0] = None
-    _FAKE.key, _FAKE.src, _FAKE.img = None, None, None
+    _FAKE.clear()
 
 
 def new_batch():

@@ -224,3 +224,55 @@ def test_dp_wire_table_tiles_the_travelling_part_of_the_flat_buffer():
     a.pending_slabs = (slab, 4, 0)
     with pytest.raises(RuntimeError):
         PL._dp_wire_table(st, [(a, None)], head=2000)                                # a deferred layer inside the factor head
+
+
+def test_armed_gradient_pass_sets_and_clears_its_flags():
+    """losses._armed, the one place a gradient pass is armed to leave weight gradients unreduced: leftovers on the armed layers
+    are gone before the body runs; inside, every flag is set; after a normal exit every flag is back at its default and what
+    the body left pending is still there (the caller consumes it); after a body that raises, nothing is pending either."""
+    from rna_gan_amd import losses as PL
+    from rna_gan_amd.engine import ConvW
+
+    def handle():
+        return ConvW(torch.zeros(64, 3, 4, 4), dw=torch.zeros(64, 3, 4, 4))
+    slab, wired, sk, g0, other = handle(), handle(), handle(), handle(), handle()
+    ops = type("Ops", (), {"_skinny_defer": None})()
+    slot, stage = torch.zeros(8), (torch.zeros(2), torch.zeros(2))
+    armed = (slab, wired, sk, g0)
+
+    def flags(cw):
+        return cw.defer_slabs, cw.wire_slot, cw.fuse_step, cw.factor_stage
+
+    def pending(cw):
+        return cw.pending_slabs, cw.pending_bias, cw.pending_wgrad
+
+    def run(body):
+        with PL._armed(slabs=[slab], wired=[(wired, slot)], skinny=(ops, sk), g0=g0, factor_stage=stage):
+            assert all(pending(cw) == (None, None, None) for cw in armed)          # leftovers dropped at entry
+            assert flags(slab) == (True, None, False, None) and flags(sk) == (False, None, False, None)
+            assert wired.defer_slabs and wired.wire_slot is slot and not wired.fuse_step
+            assert g0.fuse_step and g0.factor_stage is stage and not g0.defer_slabs
+            assert ops._skinny_defer == {sk.dw.data_ptr(): sk}
+            assert flags(other) == (False, None, False, None) and other.pending_slabs == "theirs"
+            body()
+
+    def leave():
+        slab.pending_slabs, wired.pending_slabs, g0.pending_wgrad = ("buf", 4, 0), (None, -1, 0), "staged"
+        sk.pending_slabs, sk.pending_bias = ("buf", 2, 0), ("bbuf", 2)
+
+    def leave_and_raise():
+        leave()
+        raise ValueError("the pass failed")
+
+    other.pending_slabs = "theirs"                                 # a layer that is not armed is not touched
+    slab.pending_slabs, sk.pending_bias, g0.pending_wgrad, wired.pending_wgrad = "stale", "stale", "stale", "stale"
+    run(leave)
+    assert all(flags(cw) == (False, None, False, None) for cw in armed) and ops._skinny_defer is None
+    assert pending(slab) == (("buf", 4, 0), None, None) and pending(wired) == ((None, -1, 0), None, None)
+    assert pending(sk) == (("buf", 2, 0), ("bbuf", 2), None) and pending(g0) == (None, None, "staged")
+    with pytest.raises(ValueError):
+        run(leave_and_raise)                                       # (entry drops what the first pass left)
+    assert all(flags(cw) == (False, None, False, None) for cw in armed) and ops._skinny_defer is None
+    assert all(pending(cw) == (None, None, None) for cw in armed) and other.pending_slabs == "theirs"
+    with PL._armed():                                              # nothing to arm: a plain pass
+        pass

@@ -278,8 +278,8 @@ def test_world2_factors_with_an_optimizer_that_does_not_step_from_the_wire(tmp_p
 
 def test_world2_prefix_with_paired_weight_gradients(tmp_path):
     """RNAGAN_DP_PREFIX_BWD=2 (the default): the D-loss prefix runs D(real)'s forward and data-gradient chain only; each layer's
-    conv weight gradient is one two-segment launch over the real and the fake half in the rest (engine.disc_loss_prefix_dgrad /
-    disc_loss_rest_pairw).  Same mathematics as mode 1 (real half's weight gradients written in the prefix, fake half's
+    conv weight gradient is one two-segment launch over the real and the fake half in the rest (engine.disc_loss_prefix with
+    backward="dgrad" / disc_loss_rest).  Same mathematics as mode 1 (real half's weight gradients written in the prefix, fake half's
     accumulated): fp32 kernels, fp32 wire -- rank-identical parameters, losses equal to the other route's to rounding."""
     ref = _run_world2(tmp_path, "fp32", extra_env={"RNAGAN_DP_PREFIX_BWD": "1"}, tag="_mode1")
     got = _run_world2(tmp_path, "fp32", extra_env={"RNAGAN_DP_PREFIX_BWD": "2"}, tag="_pairw")
