@@ -59,7 +59,7 @@ const char* rg_last_error(void);
  * form every fp32 product as six bf16 matrix-core products of the operands' exact three-way bf16 splits (fp32-grade accuracy,
  * ~11 % faster fp32 iteration); "wslab16": 0 keeps the deferred
  * weight-gradient slabs fp32; "bn_rev": which BatchNorm row passes walk their rows from the end (bit 2, the default: reductions); "convd": 0 sends the 64 -> 128 channel stride-2 conv back from the parity-plane-resident kernel to the
- * implicit-GEMM one, "convd_blocks": its persistent grid; "slab16": 0 keeps the split-K partial tiles of the conv launches fp32;
+ * implicit-GEMM one, "convd_blocks": its persistent grid; "slab16": 0 keeps the split-K partial tiles of the conv launches fp32 (the fp16 build's default; 1 is unsupported there);
  * "skinny128": 0 sends the image-side layers of 256 x 256 images back
  * from the control-flow-free row kernels to the general row-staged ones; "wgrad8_mfma": 32 (default) / 16 = the matrix instruction
  * shape of the 256 x 256-tile weight-gradient kernel, bit-identical results; "narrow32": 0 sends 3 x 3 convs of <= 32 output columns
@@ -398,8 +398,9 @@ int rg_bn_act_bwd_partials(const float* partial, int G, int nblk, const void* z,
  * into 64 / 128 / 256-row blocks with at most 256 workgroups (one per CU: all co-resident -- required by the hand-off). */
 int rg_conv_split(int up, int N, int Hlow, int Wlow, int O, int I, int dtype, int algo);
 /* element type of the slabs that launch leaves: RG_F32, or RG_BF16 where the 8-wave kernel stores its partial tiles as bf16
- * (option "slab16", default on: half the slab bytes written and re-read; each partial sum is rounded to bf16 before the
- * consumer adds them in fp32).  Pass it to the consumer as slab_dtype; the slab stride stays in ELEMENTS. */
+ * (option "slab16", default on in the bf16 build: half the slab bytes written and re-read; each partial sum is rounded to
+ * bf16 before the consumer adds them in fp32.  fp16 build: default OFF and unsupported -- a partial sum can leave fp16's range
+ * where the sum does not, and two partials overflowing with opposite signs add up to NaN; the slabs are RG_F32 there).  Pass it to the consumer as slab_dtype; the slab stride stays in ELEMENTS. */
 int rg_conv_slab_dtype(int up, int N, int Hlow, int Wlow, int O, int I, int dtype, int algo);
 int rg_conv_down_partial(const void* x, const void* wdn, int N, int Hi, int Wi, int I, int O, int dtype, int algo,
                          void* ws, size_t ws_bytes, void* stream);

@@ -9,7 +9,7 @@ with plain torch fp32 math.  Uses:
 It is never imported by the product path.
 
 Conventions (identical to the HIP ops):
-  * activations are NHWC tensors (N,H,W,C) of ``act_dtype`` (float32 or bfloat16); math is fp32,
+  * activations are NHWC tensors (N,H,W,C) of ``act_dtype`` (float32, bfloat16 or float16); math is fp32,
     results are rounded to ``act_dtype`` on store;
   * image-side boundary tensors are NCHW float32;
   * a conv weight is ``w[O][I][4][4]`` fp32 where O = channels on the LOW-resolution side and
@@ -64,9 +64,14 @@ class RefOps:
     def join(self):
         pass
 
+    def _q16(self, t):
+        # a 16-bit MFMA operand formed from fp32 data (weights, the image, the up-sampled image): rounded to the storage type
+        # when that is a 16-bit one (bf16 or IEEE fp16 -- the two builds of the library), used as it is otherwise
+        return t.to(self.act_dtype).to(self.f) if self.act_dtype in (torch.bfloat16, torch.float16) else t.to(self.f)
+
     def _wq(self, w):
-        # the bf16 path computes with weights rounded to bf16
-        return w.to(self.f) if self.act_dtype != torch.bfloat16 else w.to(self.act_dtype).to(self.f)
+        # the 16-bit paths compute with weights rounded to the storage type
+        return self._q16(w)
 
     # ------------------------------------------------------------------ conv family
     # (the handle's master may be stored tap-major; cw.oihw() / cw.store_grad_oihw() give the PyTorch view)
@@ -93,8 +98,8 @@ class RefOps:
     def _uppad(self, x_nhwc):
         up = F.interpolate(self._nchw(x_nhwc), scale_factor=2, mode="bilinear", align_corners=False)
         pad = F.pad(up, (1, 1, 1, 1), mode="reflect")
-        # the interpolated image is a GEMM operand: rounded to the activation dtype on the bf16 path
-        return pad if self.act_dtype != torch.bfloat16 else pad.to(torch.bfloat16).to(self.f)
+        # the interpolated image is a GEMM operand: rounded to the activation dtype on the 16-bit paths
+        return self._q16(pad)
 
     def upconv3(self, x, cw: ConvW, bias, out_nchw=False):
         y = F.conv2d(self._uppad(x), self._wq(cw.w), None if bias is None else bias.to(self.f))
@@ -129,9 +134,11 @@ class RefOps:
         if out is not None:
             out[0].copy_(self.first_down(x_nchw, cw, bias, slope))
             return out[0]
-        # bf16 path: the image-side layers run on the matrix cores too, so image and weights are rounded to
-        # bf16 operands (fp32 accumulation); the fp32 path uses the masters as they are
-        xin = x_nchw.to(self.f) if self.act_dtype != torch.bfloat16 else x_nchw.to(torch.bfloat16).to(self.f)
+        # 16-bit paths: the image-side layers run on the matrix cores too, so image and weights are rounded to
+        # 16-bit operands (fp32 accumulation); the fp32 path uses the masters as they are.  (The product rounds them only in its
+        # matrix-core row kernels -- 3 image channels, 64 or 128 on the other side; the vector kernels of every other shape take
+        # the fp32 image and weights as they are, so there this twin is faithful to a few rounding units only.)
+        xin = self._q16(x_nchw)
         y = F.conv2d(xin, self._wq(cw.w), bias, stride=2, padding=1)
         if slope != 1.0:
             y = F.leaky_relu(y, slope)

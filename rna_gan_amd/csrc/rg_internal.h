@@ -49,7 +49,15 @@ int rg_mfma_conv_bnbwd_rows(int up, int N, int Hlow, int Wlow, int O, int I, int
 int rg_mfma_conv_nsplit(int up, int N, int Hlow, int Wlow, int O, int I);
 // split-K partial tiles of the 8-wave conv kernel as bf16 instead of fp32 (option `slab16`): half the slab bytes written by the
 // conv launch and read by the fused reduction + BatchNorm kernel; the partial sums are rounded to bf16 before they are added
+// (fp16 build: fp32 slabs.  A partial sum can leave fp16's range where the whole sum does not, and two partials that overflow
+// with opposite signs add up to NaN instead of the infinity the rounded sum would store; a 16-bit partial also costs the
+// element-wise fp32-accumulation bound -- both found by tests/test_ops_exact_gpu.py.  bf16 has fp32's range: unchanged there.
+// Setting the option to 1 in the fp16 build is UNSUPPORTED: it is kept only to measure what the fp32 slabs cost.)
+#ifdef RG_HALF_F16
+constexpr int RG_SLAB16_DEFAULT = 0;
+#else
 constexpr int RG_SLAB16_DEFAULT = 1;
+#endif
 constexpr int RG_BN_REV_DEFAULT = 4;     // option bn_rev: BatchNorm row passes that walk their rows from the END (bit 0: backward-kind applies, bit 1: forward
                                          // applies, bit 2: reductions).  Measured: reductions only
 // (fp16 build: weight gradients carry the static loss scale and are the LARGE sums of the backward pass -- 2e5 was seen on the
