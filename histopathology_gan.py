@@ -72,6 +72,8 @@ EXTRA_FLAGS = [
     ("--steps_per_epoch", int, 100, "synthetic dataset length / batch"),
     ("--loss_scaling", str, "static", "fp16 only: static (fixed scale RNAGAN_F16_LOSS_SCALE) or dynamic (GradScaler-style: a step "
                                       "with a non-finite gradient is skipped and the scale halved; it grows after clean steps)"),
+    ("--critic_batchnorm", int, 1, "0 = BatchNorm-free critic (DCGANDiscriminator(batchnorm=False): biased convs, what a WGAN-GP "
+                                   "recipe uses -- the penalty is per input and train-mode BatchNorm couples the batch)"),
 ]
 
 
@@ -171,7 +173,7 @@ def main():
                       "optimizer": {"name": Adam, "args": {"lr": 0.0001, "betas": (0.5, 0.999)}}},
         "discriminator": {"name": P.DCGANDiscriminator,
                           "args": {"in_size": img_size, "in_channels": 3, "step_channels": 64,
-                                   "nonlinearity": nn.LeakyReLU(0.2), "last_nonlinearity": nn.LeakyReLU(0.2)},
+                                   "batchnorm": bool(args.critic_batchnorm), "nonlinearity": nn.LeakyReLU(0.2), "last_nonlinearity": nn.LeakyReLU(0.2)},
                           "optimizer": {"name": Adam, "args": {"lr": 0.0004, "betas": (0.5, 0.999)}}},
     }
     if args.loss_type == "wgan":

@@ -255,6 +255,11 @@ int rg_g0_wgrad(const float* z, const void* gy, float* dw, int N, int E, int C, 
  *   h[n] = sum a[n][kh][kw][c] * w[0][c][kh][kw];  out[n] = lrelu(h[n]). */
 int rg_head_fwd(const void* a, const float* w, float* h, float* out, int N, int C, float slope, int dtype,
                 void* stream);
+/* the same with the head's bias (DCGANDiscriminator(batchnorm=False)): h[n] = <a[n], w> + bias[0], added inside the kernel */
+int rg_head_fwd_bias(const void* a, const float* w, const float* bias, float* h, float* out, int N, int C, float slope,
+                     int dtype, void* stream);
+/* out[0] (+)= sum_i x[i], fixed order (the head's bias gradient sum_n gh[n]) */
+int rg_vec_sum(const float* x, int n, float* out, int accumulate, void* stream);
 /* gh[n] = coef * lrelu'(h[n])  (coef = d loss / d out[n]: -1/N, +1/N or 1; wgan_loss.py:24-29,33) */
 int rg_head_grad(const float* h, float* gh, int N, float coef, float slope, void* stream);
 /* the same with coef * 2^e, e from the exponent latched for `slot` (rg_amp_latch): part 0: e = k, 1: floor(k / 2) (the penalty's
@@ -452,6 +457,31 @@ int rg_bn_double_bwd(const void* z, const void* qa, const void* zt, const void* 
                      const float* s_gyxh, const float* s_zt, const float* s_xhzt, void* pz, float* dgamma,
                      float* dbeta, int accumulate, int M, int C, float slope, int dtype, void* ws,
                      size_t ws_bytes, void* stream);
+
+/* ---- BatchNorm-free critic layers (DCGANDiscriminator(batchnorm=False); rg_plainact.hip).  A layer is
+ *   a = lrelu(conv_down(x) + bias[c]);  backward / tangent: out = conv(.) * lrelu'(a) with the mask from the sign of the stored a.
+ * Where the plain launch does not split K (rg_conv_split <= 1) the matrix-core stride-2 conv takes either in its epilogue, on the
+ * fp32 accumulator, rounded once: rg_conv_down_epi with exactly one of shift (bias; the affine epilogue with scale 1) / mask_act
+ * (rg_conv_up already takes a mask).  Where it splits, rg_conv_down_partial / rg_conv_up_partial leave their slabs
+ * [nsplit][M][C] (element type rg_conv_slab_dtype, `stride` elements apart) and one of the two finishing kernels sums them in
+ * the fixed order s = 0, 1, ... and writes the 16-bit result:
+ *   rg_slab_bias_act:  y[m][c] = lrelu(sum_s slab[s][m][c] + bias[c], slope)
+ *   rg_slab_mask:      y[m][c] = (sum_s slab[s][m][c]) * lrelu'(mask_act[m][c]);  col_parts (optional, fp32
+ *                      [rg_slab_finish_rows(M, C)][C]): per-workgroup column sums of the STORED y -- the consumer layer's bias
+ *                      gradient once rg_parts_col_sum has added the rows up (fixed order).
+ * rg_slab_finish_rows == 0: the kernels' thread layout does not cover this C (C / 8 must divide 256 or be a multiple of it).
+ * rg_bias_act: y = lrelu(z + bias[c]) elementwise (y may be z; RG_F32 or the 16-bit type; C % 8 == 0): the pass behind a conv
+ * without a fused form (fp32 storage, generic kernels). */
+int rg_slab_finish_rows(long long M, int C);
+int rg_slab_bias_act(const void* slab, int nsplit, size_t stride, int slab_dtype, const float* bias, void* y, long long M, int C,
+                     float slope, void* stream);
+int rg_slab_mask(const void* slab, int nsplit, size_t stride, int slab_dtype, const void* mask_act, float mask_slope, void* y,
+                 float* col_parts, long long M, int C, void* stream);
+int rg_parts_col_sum(const float* parts, int rows, int C, float* out, int accumulate, void* stream);
+int rg_bias_act(const void* z, const float* bias, void* y, long long M, int C, float slope, int dtype, void* stream);
+int rg_conv_down_epi_supported(int N, int Hi, int Wi, int I, int O, int dtype, int algo);
+int rg_conv_down_epi(const void* x, const void* wdn, void* y, int N, int Hi, int Wi, int I, int O, const float* shift, float slope,
+                     const void* mask_act, float mask_slope, int dtype, int algo, void* ws, size_t ws_bytes, void* stream);
 
 /* out = g * lrelu'(a) with the mask taken from the sign of the activation OUTPUT a */
 int rg_lrelu_bwd(const void* g, const void* a, void* out, size_t n, float slope, int dtype, void* stream);

@@ -179,6 +179,15 @@ PROTOTYPES = {
     "rg_f32p_wgrad_supported": (_i, [_i, _i, _i, _i, _i, _i]),
     "rg_f32p_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i]),
     "rg_f32p_wgrad": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "rg_slab_finish_rows": (_i, [C.c_longlong, _i]),
+    "rg_slab_bias_act": (_i, [_p, _i, _z, _i, _p, _p, C.c_longlong, _i, _f, _p]),
+    "rg_slab_mask": (_i, [_p, _i, _z, _i, _p, _f, _p, _p, C.c_longlong, _i, _p]),
+    "rg_parts_col_sum": (_i, [_p, _i, _i, _p, _i, _p]),
+    "rg_bias_act": (_i, [_p, _p, _p, C.c_longlong, _i, _f, _i, _p]),
+    "rg_vec_sum": (_i, [_p, _i, _p, _i, _p]),
+    "rg_conv_down_epi_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "rg_conv_down_epi": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p, _f, _i, _i, _p, _z, _p]),
+    "rg_head_fwd_bias": (_i, [_p, _p, _p, _p, _p, _i, _i, _f, _i, _p]),
     "rg_probe_mfma_bare": (_i, [_i, _i, _i, _i, _p, _p, _p]),
     "rg_probe_lds_mfma": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
     "rg_probe_copy": (_i, [_p, _p, _z, _i, _i, _p]),
@@ -186,7 +195,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES
-ABI_VERSION = 610
+ABI_VERSION = 611
 
 _libs = {}
 LIB_PATH_F16 = os.path.join(_HERE, "librnagan_hip_f16.so")

@@ -18,7 +18,7 @@ void rg_set_error(const char* fmt, ...) {
 }
 
 // bumped whenever an entry point is added or a signature changes; rna_gan_amd/_abi.py (ABI_VERSION) refuses any other value
-extern "C" int rg_version(void) { return 610; }   // 6.10: dynamic loss scaling (rg_amp.hip, rg_adam_hyper_dev3)
+extern "C" int rg_version(void) { return 611; }   // 6.11: BatchNorm-free critic (rg_plainact.hip, rg_head_fwd_bias)
 extern "C" const char* rg_last_error(void) { return g_err; }
 
 // ---- kernel-selection knobs: override table in front of the RNAGAN_* environment variables

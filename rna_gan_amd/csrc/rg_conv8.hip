@@ -517,7 +517,7 @@ __global__ __launch_bounds__(512, 2) void conv8_kernel(G2Args a2) {
           v1.x *= rg_lmask(a.z, g.mslope); v1.y *= rg_lmask(a.z >> 16, g.mslope);
           v1.z *= rg_lmask(a.w, g.mslope); v1.w *= rg_lmask(a.w >> 16, g.mslope);
         }
-        if (g.affine) rg_affine8(v0, v1, g.scale + col, g.shift + col, g.slope);
+        if (g.affine) rg_affine8(v0, v1, g.scale + col, g.shift + col, g.slope, g.scale != nullptr);
         if (g.out_fp8) {                 // 8 OCP e4m3 values = 8 bytes (the next fp8 layer's A operand)
           int lo = 0, hi = 0;
           lo = __builtin_amdgcn_cvt_pk_fp8_f32(v0.x, v0.y, lo, false);

@@ -60,9 +60,13 @@ __device__ __forceinline__ float rg_lmask(uint32_t abits, float slope) {
   return (abits & 0x8000u) || !(abits & 0x7fffu) ? slope : 1.f;      // a <= 0 (incl. -0): slope
 }
 
-// 8 consecutive output columns: v = lrelu(v * scale[c] + shift[c], slope)
-__device__ __forceinline__ void rg_affine8(float4& v0, float4& v1, const float* sc, const float* sh, float slope) {
-  const float4 s0 = *reinterpret_cast<const float4*>(sc), s1 = *reinterpret_cast<const float4*>(sc + 4);
+// 8 consecutive output columns: v = lrelu(v * scale[c] + shift[c], slope); has_scale false (a NULL scale vector, wave-uniform):
+// scale = 1 -- a conv bias + LeakyReLU (rg_conv_down_epi)
+__device__ __forceinline__ void rg_affine8(float4& v0, float4& v1, const float* sc, const float* sh, float slope,
+                                           bool has_scale = true) {
+  const float4 one = make_float4(1.f, 1.f, 1.f, 1.f);
+  const float4 s0 = has_scale ? *reinterpret_cast<const float4*>(sc) : one;
+  const float4 s1 = has_scale ? *reinterpret_cast<const float4*>(sc + 4) : one;
   const float4 h0 = *reinterpret_cast<const float4*>(sh), h1 = *reinterpret_cast<const float4*>(sh + 4);
   v0.x = lrelu_f(v0.x * s0.x + h0.x, slope); v0.y = lrelu_f(v0.y * s0.y + h0.y, slope);
   v0.z = lrelu_f(v0.z * s0.z + h0.z, slope); v0.w = lrelu_f(v0.w * s0.w + h0.w, slope);

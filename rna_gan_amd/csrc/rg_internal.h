@@ -44,7 +44,8 @@ int rg_mfma_pack_conv_weight(const float* w, void* wdn, void* wup, int O, int I,
 int rg_mfma_pack_g0_weight(const float* w, void* wp, int E, int C, hipStream_t st);
 int rg_mfma_pack_linear_weight(const float* w, void* wp, int Nout, int K, int Nout_pad, int K_pad, hipStream_t st);
 int rg_mfma_conv_down(const void* x, const void* wdn, void* y, int N, int Hi, int Wi, int I, int O, float* stats,
-                      void* ws, size_t ws_bytes, hipStream_t st, int defer_reduce = 0, const RgBnBwdFuse* bf = nullptr);
+                      void* ws, size_t ws_bytes, hipStream_t st, int defer_reduce = 0, const RgBnBwdFuse* bf = nullptr,
+                      const float* shift = nullptr, float slope = 1.f, const void* mask = nullptr, float mslope = 1.f);
 int rg_mfma_conv_bnbwd_rows(int up, int N, int Hlow, int Wlow, int O, int I, int groups);
 int rg_mfma_conv_nsplit(int up, int N, int Hlow, int Wlow, int O, int I);
 // split-K partial tiles of the 8-wave conv kernel as bf16 instead of fp32 (option `slab16`): half the slab bytes written by the

@@ -612,7 +612,7 @@ __global__ __launch_bounds__(NT, (NSTAGE * (BM + BN) * 128 <= 80 * 1024 && NT ==
           v1.x *= rg_lmask(a.z, g.mslope); v1.y *= rg_lmask(a.z >> 16, g.mslope);
           v1.z *= rg_lmask(a.w, g.mslope); v1.w *= rg_lmask(a.w >> 16, g.mslope);
         }
-        if (g.affine) rg_affine8(v0, v1, g.scale + col, g.shift + col, g.slope);
+        if (g.affine) rg_affine8(v0, v1, g.scale + col, g.shift + col, g.slope, g.scale != nullptr);
         uint4 o;
         o.x = (uint32_t)f32_to_h16(v0.x) | ((uint32_t)f32_to_h16(v0.y) << 16);
         o.y = (uint32_t)f32_to_h16(v0.z) | ((uint32_t)f32_to_h16(v0.w) << 16);
@@ -1479,11 +1479,15 @@ int rg_mfma_conv_bnbwd_rows(int up, int N, int Hlow, int Wlow, int O, int I, int
 }
 
 int rg_mfma_conv_down(const void* x, const void* wdn, void* y, int N, int Hi, int Wi, int I, int O, float* stats,
-                      void* ws, size_t ws_bytes, hipStream_t st, int defer_reduce, const RgBnBwdFuse* bf) {
+                      void* ws, size_t ws_bytes, hipStream_t st, int defer_reduce, const RgBnBwdFuse* bf, const float* shift,
+                      float slope, const void* mask, float mslope) {
   GArgs g{};
   g.defer_reduce = defer_reduce;
   set_bwd_fuse(g, bf, N * (Hi / 2) * (Wi / 2));
-  g.stats = stats;
+  // bias + LeakyReLU (the affine epilogue with scale = 1) or the LeakyReLU mask on the accumulator: the BatchNorm-free critic
+  g.affine = shift != nullptr; g.scale = nullptr; g.shift = shift; g.slope = slope;
+  g.mask = (const uint16_t*)mask; g.mslope = mslope;
+  g.stats = (mask || shift) ? nullptr : stats;
   g.A = (const uint16_t*)x; g.B = (const uint16_t*)wdn; g.C = y;
   int Ho = Hi / 2, Wo = Wi / 2;
   g.M = N * Ho * Wo; g.Ncols = O; g.Cin = I; g.taps = 16;

@@ -479,7 +479,7 @@ __global__ void latent_prep_big_kernel(const float* u, const float* z, float* ou
 // h[n] = sum_j a[n][j] * wq[j], j = tap*C + c, wq[j] = round_T(w[c*16 + tap])
 template <typename T>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const T* a, const float* w, float* h, float* out, int C,
-                                                       float slope) {
+                                                       float slope, const float* bias) {
   // thread = channel: its 16 taps are one contiguous 64-byte weight row, and for a fixed tap the block reads
   // consecutive channels of the activation
   __shared__ float sm[4];
@@ -494,7 +494,10 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* a, const float* 
     for (int tap = 0; tap < 16; ++tap) s += Elem<T>::ld(an + (size_t)tap * C + c) * Elem<T>::round(wv[tap]);
   }
   float t = block_sum_256(s, sm);
-  if (threadIdx.x == 0) { h[n] = t; out[n] = lrelu_f(t, slope); }
+  if (threadIdx.x == 0) {
+    if (bias) t += bias[0];            // the BatchNorm-free critic's head keeps a bias (rg_head_fwd_bias)
+    h[n] = t; out[n] = lrelu_f(t, slope);
+  }
 }
 __global__ void head_grad_kernel(const float* h, float* gh, int N, float coef, float slope) {
   int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -855,8 +858,18 @@ extern "C" int rg_head_fwd(const void* a, const float* w, float* h, float* out, 
                            void* stream) {
   RG_REQUIRE(a && w && h && out && N > 0 && C > 0, RG_EINVAL, "head_fwd: bad args");
   RG_DISPATCH_DTYPE(dtype, T, {
-    hipLaunchKernelGGL((head_fwd_kernel<T>), dim3(N), dim3(256), 0, rg_stream(stream), (const T*)a, w, h, out, C, slope);
+    hipLaunchKernelGGL((head_fwd_kernel<T>), dim3(N), dim3(256), 0, rg_stream(stream), (const T*)a, w, h, out, C, slope,
+                       (const float*)nullptr);
     RG_LAUNCH_CHECK("head_fwd");
+    return RG_OK;
+  })
+}
+extern "C" int rg_head_fwd_bias(const void* a, const float* w, const float* bias, float* h, float* out, int N, int C, float slope,
+                                int dtype, void* stream) {
+  RG_REQUIRE(a && w && bias && h && out && N > 0 && C > 0, RG_EINVAL, "head_fwd_bias: bad args");
+  RG_DISPATCH_DTYPE(dtype, T, {
+    hipLaunchKernelGGL((head_fwd_kernel<T>), dim3(N), dim3(256), 0, rg_stream(stream), (const T*)a, w, h, out, C, slope, bias);
+    RG_LAUNCH_CHECK("head_fwd_bias");
     return RG_OK;
   })
 }

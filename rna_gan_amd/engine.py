@@ -138,6 +138,23 @@ class DiscNet:
             cw.version += 1
 
 
+class PlainDiscNet:
+    """BatchNorm-free discriminator (DCGANDiscriminator(batchnorm=False)): Conv+bias+LReLU, R x [Conv+bias+LReLU], head
+    Conv+bias+LReLU.  Deliberately NOT a DiscNet: the deferred-slab / wire forms of rna_gan_amd.losses gate on that class
+    and decline this one, so its weight gradients take the fp32 .dw buffers and the generic Adam / flat all-reduce path."""
+
+    def __init__(self, conv0: ConvW, blocks: List, head: ConvW, slope: float, last_slope: float):
+        self.conv0, self.blocks, self.head = conv0, blocks, head   # blocks: [ConvW with bias]
+        self.slope, self.last_slope = slope, last_slope
+
+    def convs(self):
+        return [self.conv0, self.head] + list(self.blocks)
+
+    def bump(self):
+        for cw in self.convs():
+            cw.version += 1
+
+
 class GenNet:
     """Generator as the engine sees it (torchgan DCGANGenerator recipe)."""
 
@@ -202,6 +219,8 @@ def _bn_forward(ops, z, bn: BNP, slope, update_running=True, partials=None):
 def disc_forward(ops, D: DiscNet, x_nchw, update_running=True):
     """D(x): Conv+LReLU, R x [Conv+BN(train)+LReLU], Conv(4x4 valid)+LReLU -> (N,).
     Returns (out, ctx); ctx keeps what the backward passes need."""
+    if isinstance(D, PlainDiscNet):
+        return _plain_forward(ops, D, x_nchw)
     ctx = _Ctx()
     ctx.x = x_nchw
     _refresh(ops, D.blocks)
@@ -231,6 +250,8 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
     gradient is then ONE two-segment launch over both chains (written, whatever ``accumulate`` says for the rest): the
     data-parallel D-loss step's prefix / rest pair (disc_loss_prefix(backward="dgrad") / disc_loss_rest).
     seed_part: under dynamic loss scaling, the power of the device scale the seed carries (ops.head_grad)."""
+    if isinstance(D, PlainDiscNet):
+        return _plain_backward(ops, D, ctx, coef, wgrad, accumulate, need_input_grad, keep_for_gp, input_post, partner, seed_part)
     R = len(D.blocks)
     defer_w = isinstance(wgrad, str) and wgrad == "defer"
     if defer_w:
@@ -306,6 +327,8 @@ def disc_backward_pair(ops, D: DiscNet, ctx_a, coef_a: float, ctx_b, coef_b: flo
     """Parameter gradients of sum_n coef_a*D(x_a)_n + coef_b*D(x_b)_n (written, not accumulated): the
     two backward chains run in lock step so that each layer's weight gradient is ONE two-segment
     launch (rg_conv_wgrad2) instead of two launches + two reductions.  Used by the D-loss step."""
+    if isinstance(D, PlainDiscNet):
+        return _plain_backward_pair(ops, D, ctx_a, coef_a, ctx_b, coef_b)
     R = len(D.blocks)
     gha = ops.head_grad(ctx_a.h, coef_a, D.last_slope)
     ghb = ops.head_grad(ctx_b.h, coef_b, D.last_slope)
@@ -379,6 +402,8 @@ def disc_gp_second(ops, D: DiscNet, ctx, st, accumulate: bool, need_input_grad: 
     """Steps (3)+(4): tangent forward along v and the joint reverse sweep.  Parameter gradients of lambd * penalty are
     written (accumulate=False) or added (True) into the .dw / .dbias / .dgamma / .dbeta buffers; with need_input_grad
     the gradient with respect to xhat (= the primal cotangent at the input, NCHW fp32) is returned."""
+    if isinstance(D, PlainDiscNet):
+        return _plain_gp_second(ops, D, ctx, st, accumulate, need_input_grad)
     R = len(D.blocks)
     g, v = st
     xhat = ctx.x
@@ -421,9 +446,182 @@ def disc_forward_eval(ops, D: DiscNet, x_nchw):
     """D(x) with BatchNorm in EVAL mode (running statistics) -> (N,).  The reference never evaluates its
     discriminator (every call site is in train mode); provided so that ``discriminator.eval(); discriminator(x)``
     behaves like the nn.Module it replaces."""
+    if isinstance(D, PlainDiscNet):
+        return _plain_forward(ops, D, x_nchw)[0]
     a = disc_features_eval(ops, D, x_nchw)
     _, out = ops.head_fwd(a, D.head, D.last_slope)
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# BatchNorm-free discriminator (PlainDiscNet).  a_l = lrelu(conv_down(a_{l-1}, W_l) + b_l); no pre-activation is kept: the
+# LeakyReLU mask m_l = lrelu'(a_l) is taken from the sign of the stored activation.  Train and eval mode are the same function.
+# --------------------------------------------------------------------------------------------
+def _plain_forward(ops, D: PlainDiscNet, x_nchw):
+    ctx = _Ctx()
+    ctx.x = x_nchw
+    _refresh(ops, [(cw,) for cw in D.blocks])
+    a = ops.first_down(x_nchw, D.conv0, D.conv0.bias, D.slope)
+    ctx.a = [a]
+    for cw in D.blocks:
+        a = ops.conv_down_bias_act(a, cw, cw.bias, D.slope)
+        ctx.a.append(a)
+    ctx.h, out = ops.head_fwd_bias(a, D.head, D.head.bias, D.last_slope)
+    return out, ctx
+
+
+def _plain_backward(ops, D: PlainDiscNet, ctx, coef, wgrad, accumulate, need_input_grad, keep_for_gp=False, input_post=None,
+                    partner=None, seed_part=0, gh=None):
+    """disc_backward for the BatchNorm-free net (same arguments; gh: the head cotangent when the caller already formed it).
+    gz_l = m_l * ga_l, dW_l = wgrad(gz_l, a_{l-1}), db_l = column sums of gz_l, ga_{l-1} = conv_up(gz_l, W_l) with the mask of
+    layer l-1 (and, for l > 1, the column sums that are layer l-1's bias gradient) in that conv's epilogue.  ctx.x may be a pair
+    of images (the two halves of a double batch)."""
+    R = len(D.blocks)
+    defer_w = isinstance(wgrad, str) and wgrad == "defer"
+    if defer_w:
+        ctx.gz_keep = [None] * (R + 1)
+    ctx.gx_parts = None
+    if gh is not None:
+        pass
+    elif torch.is_tensor(coef):       # N-length vector: host-side plumbing
+        gh = (coef.reshape(-1).float() * torch.where(ctx.h > 0, torch.ones_like(ctx.h),
+                                                     torch.full_like(ctx.h, D.last_slope))).contiguous()
+    elif seed_part:
+        gh = ops.head_grad(ctx.h, coef, D.last_slope, part=seed_part)
+    else:
+        gh = ops.head_grad(ctx.h, coef, D.last_slope)
+    if wgrad:
+        with ops.side(gh):
+            ops.head_wgrad(gh, ctx.a[R], D.head.dw, accumulate)
+        ops.vec_sum(gh, D.head.dbias, accumulate)
+    # the head's data gradient meets the top layer's LeakyReLU: one elementwise pass over N x 4 x 4 x C
+    gz = ops.lrelu_bwd(ops.head_bwd_data(gh, D.head), ctx.a[R], D.slope)
+    if keep_for_gp:
+        ctx.gh = gh
+        ctx.gz1 = [None] * (R + 1)
+    if wgrad and R > 0:
+        ops.col_sum(gz, D.blocks[R - 1].dbias, accumulate)
+    for l in range(R, 0, -1):
+        cw = D.blocks[l - 1]
+        if keep_for_gp:
+            ctx.gz1[l] = gz
+        if defer_w:
+            ctx.gz_keep[l] = gz
+        elif wgrad and partner is not None:
+            with ops.side(gz, partner.gz_keep[l]):
+                ops.conv_wgrad2(gz, ctx.a[l - 1], partner.gz_keep[l], partner.a[l - 1], cw, False)
+        elif wgrad:
+            with ops.side(gz):
+                ops.conv_wgrad(gz, ctx.a[l - 1], cw, accumulate)
+        if l > 1:
+            gz = ops.conv_up_mask(gz, cw, ctx.a[l - 1], D.slope, D.blocks[l - 2].dbias if wgrad else None, accumulate)
+        else:
+            gz = ops.conv_up(gz, cw, ctx.a[0], D.slope)
+    gz0 = gz
+    xs = ctx.x if isinstance(ctx.x, (tuple, list)) else (ctx.x,)
+    nx = xs[0].shape[0]
+    if keep_for_gp:
+        ctx.gz1[0] = gz0
+    if defer_w:
+        ctx.gz_keep[0] = gz0
+        ops.col_sum(gz0, D.conv0.dbias, accumulate)
+    elif wgrad and partner is not None:
+        with ops.side(gz0, partner.gz_keep[0]):
+            done = ops.skinny_wgrad(gz0, ctx.x, D.conv0.dw, False, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
+            ops.skinny_wgrad(partner.gz_keep[0], partner.x, D.conv0.dw, True)
+        if not done:
+            ops.col_sum(gz0, D.conv0.dbias, accumulate)
+    elif wgrad:
+        parts = [gz0[i * nx:(i + 1) * nx] for i in range(len(xs))] if len(xs) > 1 else [gz0]
+        with ops.side(gz0):
+            d0 = ops.skinny_wgrad(parts[0], xs[0], D.conv0.dw, accumulate, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
+            rest = [ops.skinny_wgrad(p, x, D.conv0.dw, True, dbias=D.conv0.dbias if d0 else None, dbias_accumulate=True)
+                    for p, x in zip(parts[1:], xs[1:])]
+        if not d0:
+            ops.col_sum(gz0, D.conv0.dbias, accumulate)
+        else:
+            for p, d in zip(parts[1:], rest):
+                if not d:
+                    ops.col_sum(p, D.conv0.dbias, True)
+    gx = None
+    if need_input_grad and input_post is not None:
+        fused = ops.last_up_post(gz0, D.conv0, input_post.get("tanh_img"))
+        if fused is not None:
+            gx, ctx.gx_parts = fused
+    if need_input_grad and gx is None:
+        gx = ops.last_up(gz0, D.conv0, None, False)
+    if wgrad:
+        ops.join()
+    return gx
+
+
+def _plain_backward_pair(ops, D: PlainDiscNet, ctx_a, coef_a, ctx_b, coef_b):
+    """disc_backward_pair: chain a leaves its conv operands, chain b pairs them up (one two-segment weight-gradient launch per
+    layer); the small gradients (biases, head) are written by a and added to by b."""
+    _plain_backward(ops, D, ctx_a, coef_a, "defer", False, False)
+    _plain_backward(ops, D, ctx_b, coef_b, True, True, False, partner=ctx_a)
+
+
+def _plain_loss_grads_batched(ops, G, D: PlainDiscNet, real, noise, grad_scale=1.0, next_noise=None):
+    """disc_loss_grads_batched: without BatchNorm nothing couples the samples, so D(real) and D(fake) are simply ONE 2N batch
+    -- no groups, no per-half statistics -- with the seed -1/n on the real half and +1/n on the fake half."""
+    n = real.shape[0]
+    fake_next = None
+    if next_noise is not None and isinstance(G, GenNet):
+        img2 = gen_forward_pair(ops, G, torch.cat([noise, next_noise]))
+        img, fake_next = img2[:n], img2[n:]
+    else:
+        img, _ = _gen_fwd(ops, G, noise, keep=False)
+        if next_noise is not None:
+            fake_next, _ = _gen_fwd(ops, G, next_noise, keep=False)
+    xs = (real, img)
+    _refresh(ops, [(cw,) for cw in D.blocks])
+    H, W = real.shape[2], real.shape[3]
+    C0 = D.conv0.w.shape[0]
+    a = torch.empty((2 * n, H // 2, W // 2, C0), dtype=ops.act_dtype, device=real.device)
+    bits = ops.sign_bits_for(2 * n, H // 2, W // 2, C0, D.blocks[0].O) if D.blocks else None
+    for h in range(2):
+        ops.first_down(xs[h], D.conv0, D.conv0.bias, D.slope,
+                       out=(a[h * n:(h + 1) * n], None if bits is None else bits[h * n:(h + 1) * n]))
+    if bits is not None:
+        a._rg_sign_bits = bits
+    ctx = _Ctx()
+    ctx.x, ctx.a = xs, [a]
+    for cw in D.blocks:
+        a = ops.conv_down_bias_act(a, cw, cw.bias, D.slope)
+        ctx.a.append(a)
+    ctx.h, out = ops.head_fwd_bias(a, D.head, D.head.bias, D.last_slope)
+    loss = ops.mean_diff(out[n:], out[:n], 1.0)
+    gh = torch.cat([ops.head_grad(ctx.h[:n], -grad_scale / n, D.last_slope), ops.head_grad(ctx.h[n:], grad_scale / n, D.last_slope)])
+    _plain_backward(ops, D, ctx, None, True, False, False, gh=gh)
+    return loss if next_noise is None else (loss, fake_next)
+
+
+def _plain_gp_second(ops, D: PlainDiscNet, ctx, st, accumulate, need_input_grad):
+    """disc_gp_second: the critic is piecewise linear in its input, so the gradient of <v, g(theta)> needs only the tangent
+    forward at_0 = m_0 * conv0(v), at_l = m_l * conv_down(at_{l-1}, W_l) (no bias) and one weight-gradient launch per layer
+    against the first backward's gz1 -- no primal cotangent, no joint reverse sweep.  Every bias gradient and the gradient
+    with respect to xhat are EXACTLY zero: written as zeros (accumulate False) or left alone."""
+    R = len(D.blocks)
+    g, v = st
+    at = ops.first_down_tangent(v, D.conv0, ctx.a[0], D.slope)
+    ats = [at]
+    for l in range(1, R + 1):
+        at = ops.conv_down_mask(at, D.blocks[l - 1], ctx.a[l], D.slope)
+        ats.append(at)
+    with ops.side():
+        ops.head_wgrad(ctx.gh, ats[R], D.head.dw, accumulate)
+    for l in range(R, 0, -1):
+        with ops.side():
+            ops.conv_wgrad(ctx.gz1[l], ats[l - 1], D.blocks[l - 1], accumulate)
+    with ops.side(v):
+        ops.skinny_wgrad(ctx.gz1[0], v, D.conv0.dw, accumulate)
+    if not accumulate:
+        for cw in D.convs():
+            ops.zero_(cw.dbias)
+    gx = ops.zero_(torch.empty_like(ctx.x)) if need_input_grad else None
+    ops.join()
+    return gx
 
 
 # --------------------------------------------------------------------------------------------
@@ -667,6 +865,8 @@ def disc_loss_grads_batched(ops, G, D: DiscNet, real, noise, grad_scale: float =
     backward reductions, parameter gradients summed).  Same result as disc_loss_grads up to the kernels' tile shapes.
     next_noise: also produce G(next_noise) -- the fake batch of the penalty step that follows (same generator weights) -- in
     the same generator pass (gen_forward_pair); returns (loss, fake_next) then."""
+    if isinstance(D, PlainDiscNet):
+        return _plain_loss_grads_batched(ops, G, D, real, noise, grad_scale, next_noise)
     n = real.shape[0]
     R = len(D.blocks)
     fake_next = None
@@ -802,22 +1002,37 @@ def tap_major_(mod):
     return mod
 
 
-def build_disc_net(mod) -> DiscNet:
+def build_disc_net(mod):
     blocks = list(mod.model.children())
     c0 = blocks[0][0]
     conv0 = ConvW(c0.weight.data, c0.bias.data, _grad_of(c0.weight), _grad_of(c0.bias))
     slope = _slope_of(blocks[0][-1], 0.2)
+    hc = mod.disc[0]
+    if hc.bias is not None:
+        return _build_plain_disc_net(mod, conv0, slope)
     bl = []
     for blk in blocks[1:]:
         conv, bn = blk[0], blk[1]
         if conv.bias is not None or not isinstance(bn, torch.nn.BatchNorm2d):
-            raise NotImplementedError("HIP path supports the batchnorm=True recipe only")
+            raise NotImplementedError("HIP path supports the batchnorm=True recipe and the all-bias batchnorm=False recipe only")
         bl.append((ConvW.from_param(conv.weight, _grad_of(conv.weight)), _bnp(bn)))
-    hc = mod.disc[0]
-    if hc.bias is not None:
-        raise NotImplementedError("HIP path supports the batchnorm=True recipe only")
     head = ConvW(hc.weight.data, None, _grad_of(hc.weight))
     return DiscNet(conv0, bl, head, slope, _slope_of(mod.disc[-1], 0.2))
+
+
+def _build_plain_disc_net(mod, conv0, slope) -> PlainDiscNet:
+    """batchnorm=False recipe: every block is [Conv2d(bias=True), nl] and the head conv has a bias."""
+    bl = []
+    for blk in list(mod.model.children())[1:]:
+        conv = blk[0]
+        if conv.bias is None or any(isinstance(m, torch.nn.BatchNorm2d) for m in blk):
+            raise NotImplementedError("HIP path supports the batchnorm=True recipe and the all-bias batchnorm=False recipe only")
+        cw = ConvW.from_param(conv.weight, _grad_of(conv.weight))
+        cw.bias, cw.dbias = conv.bias.data, _grad_of(conv.bias)
+        bl.append(cw)
+    hc = mod.disc[0]
+    head = ConvW(hc.weight.data, hc.bias.data, _grad_of(hc.weight), _grad_of(hc.bias))
+    return PlainDiscNet(conv0, bl, head, slope, _slope_of(mod.disc[-1], 0.2))
 
 
 def build_gen_net(mod) -> GenNet:
@@ -869,6 +1084,8 @@ def upgen_forward_eval(ops, G: UpGenNet, noise):
 def disc_features_eval(ops, D: DiscNet, x_nchw):
     """Discriminator trunk with BatchNorm in EVAL mode (running statistics): the activation in front of the head,
     NHWC (N, 4, 4, C).  Feature extractor of the Frechet-distance proxy (rna_gan_amd.fid)."""
+    if isinstance(D, PlainDiscNet):
+        return _plain_forward(ops, D, x_nchw)[1].a[-1]
     a = ops.first_down(x_nchw, D.conv0, D.conv0.bias, D.slope)
     for cw, bn in D.blocks:
         z = ops.conv_down(a, cw)

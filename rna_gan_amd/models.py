@@ -402,13 +402,13 @@ class DCGANUpGenerator(Generator):
 
 
 class DCGANDiscriminator(Discriminator):
-    """Conv(c,d,4,2,1,bias)+nl ; R x [Conv(d,2d,4,2,1)+BN+nl] ; disc = Conv(d,1,4,1,0)+last_nl -> (N,)."""
+    """Conv(c,d,4,2,1,bias)+nl ; R x [Conv(d,2d,4,2,1)+BN+nl] ; disc = Conv(d,1,4,1,0)+last_nl -> (N,).
+    batchnorm=False (the critic a WGAN-GP recipe asks for: the penalty is defined per input and train-mode BatchNorm couples
+    the samples of a batch): R x [Conv(d,2d,4,2,1,bias)+nl] and a biased head conv, engine.PlainDiscNet."""
 
     def __init__(self, in_size=32, in_channels=3, step_channels=64, batchnorm=True, nonlinearity=None,
                  last_nonlinearity=None, label_type="none"):
         super().__init__(in_channels, label_type)
-        if not batchnorm:
-            raise NotImplementedError("rna_gan_amd implements the batchnorm=True recipe used by RNA-GAN")
         reps = _num_repeats(in_size, "Input Image Size")
         self.n = step_channels
         nl = nn.LeakyReLU(0.2) if nonlinearity is None else nonlinearity
@@ -416,10 +416,13 @@ class DCGANDiscriminator(Discriminator):
         d = self.n
         model: List[nn.Module] = [nn.Sequential(nn.Conv2d(self.input_dims, d, 4, 2, 1, bias=True), nl)]
         for _ in range(reps):
-            model.append(nn.Sequential(nn.Conv2d(d, d * 2, 4, 2, 1, bias=False), nn.BatchNorm2d(d * 2), nl))
+            if batchnorm:
+                model.append(nn.Sequential(nn.Conv2d(d, d * 2, 4, 2, 1, bias=False), nn.BatchNorm2d(d * 2), nl))
+            else:
+                model.append(nn.Sequential(nn.Conv2d(d, d * 2, 4, 2, 1, bias=True), nl))
             d *= 2
         self.model = nn.Sequential(*model)
-        self.disc = nn.Sequential(nn.Conv2d(d, 1, 4, 1, 0, bias=False), last_nl)
+        self.disc = nn.Sequential(nn.Conv2d(d, 1, 4, 1, 0, bias=not batchnorm), last_nl)
         self._weight_initializer()
 
     def _build_net(self):

@@ -193,6 +193,7 @@ class HipOps:
         self.f32_planes = int(os.environ.get("RNAGAN_F32_PLANES", "6")) if self.dt == RG_F32 else 0
         if self.f32_planes not in (0, 3, 6):
             raise ValueError("RNAGAN_F32_PLANES must be 0, 3 or 6")
+        self.plain_paths = {}         # BatchNorm-free critic layers: how many launches took which form (conv_down_bias_act)
         self._slabs_pending = None    # the tensor whose deferred split-K slabs currently occupy the workspace
         self._sb_sync = None          # hand-off words of the fused kernels: zeroed once, left zero by every launch
         self._sb_scratch = None
@@ -515,6 +516,139 @@ class HipOps:
             self.lib.rg_conv_up(_ptr(x), _ptr(cw.w), _ptr(wup), _ptr(y), N, Ho, Wo, O, I, _ptr(mask_act), float(slope),
                                 _ptr(st), self.dt, self.algo, _ptr(ws), ws.numel(), self.stream), "rg_conv_up"), cw=cw)
         return (y, st) if want_stats else y
+
+    # ------------------------------------------------------------------ BatchNorm-free critic layers (rg_plainact.hip)
+    # path: None = the fused form this shape has ("slab": split-K launch + finishing kernel; "epilogue": in the unsplit conv's
+    # epilogue), "unfused" = the conv as it stands followed by the separate elementwise pass (what fp32 storage and the generic
+    # kernels always run, and what the op tests compare the fused forms with).  plain_paths counts which one ran.
+    def _plain_fused(self, up, N, Hl, Wl, O, I, M, C, path):
+        """(kind, nsplit) of the fused form of a plain-critic conv: ("slab", ns), ("epilogue", 1) or (None, 1)."""
+        if path == "unfused" or self.dt == RG_F32:
+            return None, 1
+        ns = int(self.lib.rg_conv_split(up, N, Hl, Wl, O, I, self.dt, self.algo))
+        if ns > 1:
+            return ("slab", ns) if self.lib.rg_slab_finish_rows(M, C) > 0 else (None, 1)
+        return "epilogue", 1
+
+    def _count_path(self, kind):
+        self.plain_paths[kind or "unfused"] = self.plain_paths.get(kind or "unfused", 0) + 1
+
+    def _partial(self, up, x, wpk, N, Hl, Wl, O, I, cw):
+        """The split-K launch alone: (workspace holding the slabs, their element type)."""
+        ws = self._ws(self.lib.rg_conv_workspace_bytes(up, N, Hl, Wl, O, I, self.dt, self.algo))
+        if up:
+            fn = lambda: check(self.lib.rg_conv_up_partial(_ptr(x), _ptr(wpk), N, Hl, Wl, O, I, self.dt, self.algo, _ptr(ws),
+                                                           ws.numel(), self.stream), "rg_conv_up_partial")
+        else:
+            fn = lambda: check(self.lib.rg_conv_down_partial(_ptr(x), _ptr(wpk), N, 2 * Hl, 2 * Wl, I, O, self.dt, self.algo,
+                                                             _ptr(ws), ws.numel(), self.stream), "rg_conv_down_partial")
+        self._timed("conv_fwd_dgrad", 2.0 * N * Hl * Wl * O * I * 16, fn, cw=cw)
+        return ws, int(self.lib.rg_conv_slab_dtype(up, N, Hl, Wl, O, I, self.dt, self.algo))
+
+    def _conv_down_epi(self, x, cw, y, N, Hi, Wi, I, O, bias, slope, mask, mslope):
+        wdn, _ = self._packs(cw)
+        ws = self._ws(self.lib.rg_conv_workspace_bytes(0, N, Hi // 2, Wi // 2, O, I, self.dt, self.algo))
+        self._timed("conv_fwd_dgrad", 2.0 * N * (Hi // 2) * (Wi // 2) * O * I * 16, lambda: check(
+            self.lib.rg_conv_down_epi(_ptr(x), _ptr(wdn), _ptr(y), N, Hi, Wi, I, O, _ptr(bias), float(slope), _ptr(mask),
+                                      float(mslope), self.dt, self.algo, _ptr(ws), ws.numel(), self.stream),
+            "rg_conv_down_epi"), cw=cw)
+
+    def conv_down_bias_act(self, x, cw: ConvW, bias, slope: float, path=None):
+        """lrelu(conv_down(x) + bias[c], slope), rounded once from the fp32 accumulator in the fused forms."""
+        N, Hi, Wi, I = x.shape
+        O = cw.O
+        self._tap_major(cw)
+        assert cw.I == I and x.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == O and bias.is_contiguous()
+        M = N * (Hi // 2) * (Wi // 2)
+        kind, ns = self._plain_fused(0, N, Hi // 2, Wi // 2, O, I, M, O, path)
+        if kind == "epilogue" and (bias.data_ptr() % 16 or
+                                   not self.lib.rg_conv_down_epi_supported(N, Hi, Wi, I, O, self.dt, self.algo)):
+            kind = None
+        self._count_path(kind)
+        if kind is None:
+            y = self.conv_down(x, cw)
+            if hasattr(y, "_rg_planes"):
+                del y._rg_planes
+            check(self.lib.rg_bias_act(_ptr(y), _ptr(bias), _ptr(y), M, O, float(slope), self.dt, self.stream), "rg_bias_act")
+            return y
+        y = self._act(N, Hi // 2, Wi // 2, O)
+        if kind == "slab":
+            ws, sdt = self._partial(0, x, self._packs(cw)[0], N, Hi // 2, Wi // 2, O, I, cw)
+            self._timed("plain_finish", 0.0, lambda: check(
+                self.lib.rg_slab_bias_act(_ptr(ws), ns, y.numel(), sdt, _ptr(bias), _ptr(y), M, O, float(slope), self.stream),
+                "rg_slab_bias_act"))
+        else:
+            self._conv_down_epi(x, cw, y, N, Hi, Wi, I, O, bias, slope, None, 1.0)
+        return y
+
+    def conv_down_mask(self, x, cw: ConvW, mask_act, slope: float, path=None):
+        """conv_down(x) * lrelu'(mask_act) (no bias): a layer of the penalty's tangent forward."""
+        N, Hi, Wi, I = x.shape
+        O = cw.O
+        self._tap_major(cw)
+        assert cw.I == I and x.is_contiguous()
+        assert mask_act.shape == (N, Hi // 2, Wi // 2, O) and mask_act.dtype == self.act_dtype and mask_act.is_contiguous()
+        M = N * (Hi // 2) * (Wi // 2)
+        kind, ns = self._plain_fused(0, N, Hi // 2, Wi // 2, O, I, M, O, path)
+        if kind == "epilogue" and not self.lib.rg_conv_down_epi_supported(N, Hi, Wi, I, O, self.dt, self.algo):
+            kind = None
+        self._count_path(kind)
+        if kind is None:
+            return self.lrelu_bwd(self.conv_down(x, cw), mask_act, slope)
+        y = self._act(N, Hi // 2, Wi // 2, O)
+        if kind == "slab":
+            ws, sdt = self._partial(0, x, self._packs(cw)[0], N, Hi // 2, Wi // 2, O, I, cw)
+            self._timed("plain_finish", 0.0, lambda: check(
+                self.lib.rg_slab_mask(_ptr(ws), ns, y.numel(), sdt, _ptr(mask_act), float(slope), _ptr(y), None, M, O,
+                                      self.stream), "rg_slab_mask"))
+        else:
+            self._conv_down_epi(x, cw, y, N, Hi, Wi, I, O, None, 1.0, mask_act, slope)
+        return y
+
+    def conv_up_mask(self, x, cw: ConvW, mask_act, slope: float, dbias=None, accumulate=False, path=None):
+        """gz = conv_up(x) * lrelu'(mask_act), and dbias (+)= the column sums of gz (the bias gradient of the layer whose
+        activation mask_act is).  A launch that splits K leaves its slabs to the mask-finishing kernel, which also leaves the
+        per-workgroup column sums; an unsplit one takes the mask in its epilogue (conv_up) and the sums come from col_sum."""
+        N, Ho, Wo, O = x.shape
+        I = cw.I
+        self._tap_major(cw)
+        assert cw.O == O and x.is_contiguous()
+        assert mask_act.shape == (N, 2 * Ho, 2 * Wo, I) and mask_act.dtype == self.act_dtype and mask_act.is_contiguous()
+        M = N * 4 * Ho * Wo
+        kind, ns = self._plain_fused(1, N, Ho, Wo, O, I, M, I, path)
+        self._count_path(kind)
+        if kind != "slab":
+            y = self.conv_up(x, cw, mask_act, slope) if path != "unfused" else self.lrelu_bwd(self.conv_up(x, cw), mask_act, slope)
+            if dbias is not None:
+                self.col_sum(y, dbias, accumulate)
+            return y
+        y = self._act(N, 2 * Ho, 2 * Wo, I)
+        ws, sdt = self._partial(1, x, self._packs(cw)[1], N, Ho, Wo, O, I, cw)
+        rows = int(self.lib.rg_slab_finish_rows(M, I))
+        parts = self._f32(rows, I) if dbias is not None else None
+        self._timed("plain_finish", 0.0, lambda: check(
+            self.lib.rg_slab_mask(_ptr(ws), ns, y.numel(), sdt, _ptr(mask_act), float(slope), _ptr(y), _ptr(parts), M, I,
+                                  self.stream), "rg_slab_mask"))
+        if dbias is not None:
+            check(self.lib.rg_parts_col_sum(_ptr(parts), rows, I, _ptr(dbias), int(accumulate), self.stream), "rg_parts_col_sum")
+        return y
+
+    def head_fwd_bias(self, a, cw: ConvW, bias, slope: float):
+        N, C = a.shape[0], a.shape[3]
+        assert a.shape[1] == 4 and a.shape[2] == 4 and a.is_contiguous() and bias.numel() == 1
+        h, out = self._f32(N), self._f32(N)
+        check(self.lib.rg_head_fwd_bias(_ptr(a), _ptr(cw.w), _ptr(bias), _ptr(h), _ptr(out), N, C, float(slope), self.dt,
+                                        self.stream), "rg_head_fwd_bias")
+        return h, out
+
+    def vec_sum(self, v, out, accumulate: bool):
+        """out[0] (+)= sum(v) (fp32 vector of batch length: the head's bias gradient)."""
+        assert v.dtype == torch.float32 and v.is_contiguous() and out.numel() == 1
+        check(self.lib.rg_vec_sum(_ptr(v), v.numel(), _ptr(out), int(accumulate), self.stream), "rg_vec_sum")
+
+    def zero_(self, t):
+        """Exact zeros (the penalty step's bias gradients, DESIGN): a fill on the stream, no arithmetic."""
+        return t.zero_()
 
     def conv_up_affine(self, x, cw: ConvW, scale, shift, slope: float):
         """Transposed conv with the eval-mode BatchNorm affine and LeakyReLU fused into its epilogue (bf16 MFMA path):
