@@ -609,7 +609,8 @@ int rg_storage_dtype(void);
  *   weight   dW = dy^T . x      A = dy^T [out][N]    B = x^T [in][N]       (both transposed packs; K = batch)
  * rg_gemm_nt_bf16: bf16 operands with K padded to K_pad (multiple of 64, zero filled), fp32 accumulate/output,
  *   epilogue y = lrelu(acc * scale[j] + shift[j], slope) (scale/shift may be NULL, slope 1 = none).  Nout need not
- *   be a multiple of 8; the columns up to the next multiple of 8 (when inside ldy) are zero-filled.
+ *   be a multiple of 8; the columns Nout .. min(roundup8(Nout), ldy) - 1 are written as +0.0 (for every ldy, aligned or
+ *   not), the columns from there to ldy - 1 are left untouched.
  * rg_transpose_pack_bf16: dst bf16 [C_pad][R_pad] = src^T (fp32 [R][C]), zero padded; R_pad % 64 == 0.
  * rg_transpose_f32: fp32 parity mode (the functor GEMM rg_linear_affine_act takes fp32 operands).
  * ------------------------------------------------------------------------------------------- */

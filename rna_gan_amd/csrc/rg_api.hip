@@ -18,7 +18,7 @@ void rg_set_error(const char* fmt, ...) {
 }
 
 // bumped whenever an entry point is added or a signature changes; rna_gan_amd/_abi.py (ABI_VERSION) refuses any other value
-extern "C" int rg_version(void) { return 611; }   // 6.11: BatchNorm-free critic (rg_plainact.hip, rg_head_fwd_bias)
+extern "C" int rg_version(void) { return 612; }   // 6.12: rg_gemm_nt_bf16 zero-fills its pad columns for every ldy (ragged scalar epilogue)
 extern "C" const char* rg_last_error(void) { return g_err; }
 
 // ---- kernel-selection knobs: override table in front of the RNAGAN_* environment variables

@@ -70,7 +70,7 @@ __global__ void nchw_to_nhwc_affine_kernel(const float* __restrict__ x, float* _
     const size_t r = i / C;
     const int p = (int)(r % HW);
     const int n = (int)(r / HW);
-    y[i] = x[((size_t)n * C + c) * HW + p] * scale[c] + shift[c];
+    y[i] = fmaf(x[((size_t)n * C + c) * HW + p], scale[c], shift[c]);      // one rounding
   }
 }
 

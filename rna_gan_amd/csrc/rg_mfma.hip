@@ -641,8 +641,10 @@ __global__ __launch_bounds__(NT, (NSTAGE * (BM + BN) * 128 <= 80 * 1024 && NT ==
           *reinterpret_cast<float4*>(yo + 4) = make_float4(vals[4], vals[5], vals[6], vals[7]);
         } else {                                             // ragged row end (Ncols % 8 != 0) / unaligned rows
 #pragma unroll
-          for (int e = 0; e < 8; ++e)
+          for (int e = 0; e < 8; ++e) {
             if (col + e < g.Ncols) yo[e] = vals[e];
+            else if (col + e < g.ldc) yo[e] = 0.f;           // pad columns up to the next multiple of 8 inside the row: zero
+          }
         }
       }
     }

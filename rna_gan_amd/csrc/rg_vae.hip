@@ -75,10 +75,12 @@ __global__ void dropout_kernel(const float* __restrict__ x, const uint8_t* __res
   }
 }
 // z = mu + eps * exp(0.5 * logvar)    (src/betaVAE.py:96-100)
+// The product and the sum are formed in fp64 and rounded once (HBM-bound: the fp64 operations are free), so the error is expf's
+// (1 ulp of the second term) plus one rounding of z: at most 4 units 2^-24 of the larger term.  Likewise in the backward.
 __global__ void reparam_kernel(const float* __restrict__ mu, const float* __restrict__ lv, const float* __restrict__ eps,
                                float* __restrict__ z, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    z[i] = mu[i] + eps[i] * expf(0.5f * lv[i]);
+    z[i] = (float)((double)mu[i] + (double)eps[i] * (double)expf(0.5f * lv[i]));
 }
 // gmu = gmu_loss + gz ; glv = glv_loss + gz * eps * 0.5 * exp(0.5 * logvar)
 __global__ void reparam_bwd_kernel(const float* __restrict__ gz, const float* __restrict__ lv, const float* __restrict__ eps,
@@ -87,7 +89,7 @@ __global__ void reparam_bwd_kernel(const float* __restrict__ gz, const float* __
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float g = gz[i];
     gmu[i] = (gmu_loss ? gmu_loss[i] : 0.f) + g;
-    glv[i] = (glv_loss ? glv_loss[i] : 0.f) + g * eps[i] * 0.5f * expf(0.5f * lv[i]);
+    glv[i] = (float)((glv_loss ? (double)glv_loss[i] : 0.0) + (double)g * (double)eps[i] * 0.5 * (double)expf(0.5f * lv[i]));
   }
 }
 __global__ void add_kernel(float* __restrict__ y, const float* __restrict__ x, size_t n) {
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256) void vae_loss_partial_kernel(const float* __re
                                                                float* __restrict__ gxr, size_t nx, float gx_scale,
                                                                const float* __restrict__ mu, const float* __restrict__ lv,
                                                                float* __restrict__ gmu, float* __restrict__ glv, size_t nz,
-                                                               float gz_scale, float* __restrict__ partial) {
+                                                               double gz_scale, float* __restrict__ partial) {
   __shared__ float sm[4];
   const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   float s1 = 0.f, s2 = 0.f;
@@ -115,8 +117,9 @@ __global__ __launch_bounds__(256) void vae_loss_partial_kernel(const float* __re
   for (size_t i = t0; i < nz; i += stride) {
     const float m = mu[i], l = lv[i], e = expf(l);
     s2 += 1.f + l - m * m - e;
-    gmu[i] = gz_scale * m;                          // beta * d kld / d mu = beta * mu / N
-    glv[i] = gz_scale * 0.5f * (e - 1.f);           // beta * d kld / d lv = beta * 0.5 (exp(lv) - 1) / N
+    // (gz_scale = beta / N and the products in fp64, rounded once: expf's error and one rounding are all that is left)
+    gmu[i] = (float)(gz_scale * (double)m);                        // beta * d kld / d mu = beta * mu / N
+    glv[i] = (float)(gz_scale * 0.5 * ((double)e - 1.0));          // beta * d kld / d lv = beta * 0.5 (exp(lv) - 1) / N
   }
   const float a = block_sum_256(s1, sm);
   const float b = block_sum_256(s2, sm);
@@ -211,7 +214,7 @@ extern "C" int rg_vae_loss(const float* x, const float* x_recons, int N, int F, 
   const float inv_nf = 1.0f / ((float)N * (float)F), inv_n = 1.0f / (float)N;
   // the KL gradients only flow when training (total = recons + beta * kld); in evaluation total = recons
   hipLaunchKernelGGL(vae_loss_partial_kernel, dim3(nb), dim3(256), 0, rg_stream(stream), x, x_recons, g_recons, nx,
-                     2.0f * inv_nf, z_mean, z_logvar, g_mean, g_logvar, nz, training ? beta * inv_n : 0.f, (float*)ws);
+                     2.0f * inv_nf, z_mean, z_logvar, g_mean, g_logvar, nz, training ? (double)beta / (double)N : 0.0, (float*)ws);
   RG_LAUNCH_CHECK("vae_loss");
   hipLaunchKernelGGL(vae_loss_final_kernel, dim3(1), dim3(256), 0, rg_stream(stream), (const float*)ws, (int)nb, inv_nf, inv_n,
                      beta, training, losses);
