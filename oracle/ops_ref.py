@@ -55,15 +55,6 @@ class RefOps:
     def _nchw(self, x):
         return x.to(self.f).permute(0, 3, 1, 2)
 
-    from contextlib import contextmanager as _cm
-
-    @_cm
-    def side(self, *tensors):
-        yield
-
-    def join(self):
-        pass
-
     def _q16(self, t):
         # a 16-bit MFMA operand formed from fp32 data (weights, the image, the up-sampled image): rounded to the storage type
         # when that is a 16-bit one (bf16 or IEEE fp16 -- the two builds of the library), used as it is otherwise
@@ -75,11 +66,11 @@ class RefOps:
 
     # ------------------------------------------------------------------ conv family
     # (the handle's master may be stored tap-major; cw.oihw() / cw.store_grad_oihw() give the PyTorch view)
-    def conv_down(self, x, cw: ConvW, want_stats=False, defer=0, bn_bwd=None):      # defer: a launch-fusion hint of the HIP backend
+    def conv_down(self, x, cw: ConvW, want_stats=False, defer=0):      # defer: a launch-fusion hint of the HIP backend
         y = _nhwc(F.conv2d(self._nchw(x), self._wq(cw.oihw()), None, stride=2, padding=1), self.act_dtype)
         return (y, None) if want_stats else y          # the twin has no fused statistics: bn_forward computes them
 
-    def conv_up(self, x, cw: ConvW, mask_act=None, slope=1.0, want_stats=False, defer=0, bn_bwd=None):
+    def conv_up(self, x, cw: ConvW, mask_act=None, slope=1.0, want_stats=False, defer=0):
         y = F.conv_transpose2d(self._nchw(x), self._wq(cw.oihw()), None, stride=2, padding=1)
         if mask_act is not None:       # fused LeakyReLU backward: applied to the fp32 result, rounded once
             y = y * _lrelu_mask(self._nchw(mask_act), slope)

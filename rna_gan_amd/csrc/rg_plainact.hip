@@ -244,6 +244,6 @@ extern "C" int rg_conv_down_epi(const void* x, const void* wdn, void* y, int N, 
   RG_REQUIRE(rg_conv_down_epi_supported(N, Hi, Wi, I, O, dtype, algo), RG_EUNSUPPORTED,
              "conv_down_epi: shape / dtype not supported by the MFMA kernel");
   RG_REQUIRE(pa_aligned16(shift) && pa_aligned16(mask_act) && pa_aligned16(y), RG_EINVAL, "conv_down_epi: 16-byte aligned buffers required");
-  return rg_mfma_conv_down(x, wdn, y, N, Hi, Wi, I, O, nullptr, ws, ws_bytes, rg_stream(stream), 0, nullptr, shift, slope,
+  return rg_mfma_conv_down(x, wdn, y, N, Hi, Wi, I, O, nullptr, ws, ws_bytes, rg_stream(stream), 0, shift, slope,
                            mask_act, mask_slope);
 }

@@ -191,13 +191,6 @@ class _Ctx:
     pass
 
 
-def _bnb(zs, means, invstds, blocks, l, slope, groups):
-    """(z, mean, invstd, gamma, beta, slope, groups) of discriminator block l: what a data-gradient conv needs to produce that
-    block's BatchNorm-backward sums in its own epilogue (HIP backend; the twin ignores it)."""
-    bn = blocks[l - 1][1]
-    return (zs[l], means[l], invstds[l], bn.gamma, bn.beta, slope, groups)
-
-
 def _refresh(ops, blocks):
     """Before a network's first conv of a pass: stale bf16 weight images of all its layers rebuilt in one launch (HIP backend)."""
     fn = getattr(ops, "refresh_packs", None)
@@ -265,8 +258,7 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
     else:
         gh = ops.head_grad(ctx.h, coef, D.last_slope)
     if wgrad:
-        with ops.side(gh):
-            ops.head_wgrad(gh, ctx.a[R], D.head.dw, accumulate)
+        ops.head_wgrad(gh, ctx.a[R], D.head.dw, accumulate)
     ga = ops.head_bwd_data(gh, D.head)
     if keep_for_gp:
         ctx.gh = gh
@@ -284,15 +276,12 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
         if defer_w:
             ctx.gz_keep[l] = gz
         elif wgrad and partner is not None:
-            with ops.side(gz, partner.gz_keep[l]):
-                ops.conv_wgrad2(gz, ctx.a[l - 1], partner.gz_keep[l], partner.a[l - 1], cw, False)
+            ops.conv_wgrad2(gz, ctx.a[l - 1], partner.gz_keep[l], partner.a[l - 1], cw, False)
         elif wgrad:
-            with ops.side(gz):
-                ops.conv_wgrad(gz, ctx.a[l - 1], cw, accumulate)
+            ops.conv_wgrad(gz, ctx.a[l - 1], cw, accumulate)
         # the data gradient of layer 1 feeds layer 0's LeakyReLU: its backward is fused into the epilogue
         # (defer=1: the next op on ga is the BatchNorm backward of the layer below, which reduces split-K slabs itself)
-        ga = ops.conv_up(gz, cw, defer=1, bn_bwd=_bnb(ctx.z, ctx.mean, ctx.invstd, D.blocks, l - 1, D.slope, 1)) if l > 1 \
-            else ops.conv_up(gz, cw, ctx.a[0], D.slope)
+        ga = ops.conv_up(gz, cw, defer=1) if l > 1 else ops.conv_up(gz, cw, ctx.a[0], D.slope)
     gz0 = ga if R > 0 else ops.lrelu_bwd(ga, ctx.a[0], D.slope)
     if keep_for_gp:
         ctx.gz1[0] = gz0
@@ -300,15 +289,13 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
         ctx.gz_keep[0] = gz0
         ops.col_sum(gz0, D.conv0.dbias, accumulate)
     elif wgrad and partner is not None:
-        with ops.side(gz0, partner.gz_keep[0]):
-            # (dbias: the kernel forms the bias gradient -- the column sums of gz0 -- in the same pass where it can)
-            done = ops.skinny_wgrad(gz0, ctx.x, D.conv0.dw, False, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
-            ops.skinny_wgrad(partner.gz_keep[0], partner.x, D.conv0.dw, True)
+        # (dbias: the kernel forms the bias gradient -- the column sums of gz0 -- in the same pass where it can)
+        done = ops.skinny_wgrad(gz0, ctx.x, D.conv0.dw, False, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
+        ops.skinny_wgrad(partner.gz_keep[0], partner.x, D.conv0.dw, True)
         if not done:
             ops.col_sum(gz0, D.conv0.dbias, accumulate)
     elif wgrad:
-        with ops.side(gz0):
-            done = ops.skinny_wgrad(gz0, ctx.x, D.conv0.dw, accumulate, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
+        done = ops.skinny_wgrad(gz0, ctx.x, D.conv0.dw, accumulate, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
         if not done:
             ops.col_sum(gz0, D.conv0.dbias, accumulate)
     gx = None
@@ -318,8 +305,6 @@ def disc_backward(ops, D: DiscNet, ctx, coef: float, wgrad, accumulate: bool,
             gx, ctx.gx_parts = fused
     if need_input_grad and gx is None:
         gx = ops.last_up(gz0, D.conv0, None, False)
-    if wgrad:
-        ops.join()
     return gx
 
 
@@ -332,9 +317,8 @@ def disc_backward_pair(ops, D: DiscNet, ctx_a, coef_a: float, ctx_b, coef_b: flo
     R = len(D.blocks)
     gha = ops.head_grad(ctx_a.h, coef_a, D.last_slope)
     ghb = ops.head_grad(ctx_b.h, coef_b, D.last_slope)
-    with ops.side(gha, ghb):
-        ops.head_wgrad(gha, ctx_a.a[R], D.head.dw, False)
-        ops.head_wgrad(ghb, ctx_b.a[R], D.head.dw, True)
+    ops.head_wgrad(gha, ctx_a.a[R], D.head.dw, False)
+    ops.head_wgrad(ghb, ctx_b.a[R], D.head.dw, True)
     ga_a = ops.head_bwd_data(gha, D.head)
     ga_b = ops.head_bwd_data(ghb, D.head)
     for l in range(R, 0, -1):
@@ -343,8 +327,7 @@ def disc_backward_pair(ops, D: DiscNet, ctx_a, coef_a: float, ctx_b, coef_b: flo
                                     bn.dgamma, bn.dbeta, False, keep_ga=False)
         gz_b, _, _ = ops.bn_act_bwd(ctx_b.z[l], ga_b, ctx_b.mean[l], ctx_b.invstd[l], bn.gamma, bn.beta, D.slope,
                                     bn.dgamma, bn.dbeta, True, keep_ga=False)
-        with ops.side(gz_a, gz_b):
-            ops.conv_wgrad2(gz_a, ctx_a.a[l - 1], gz_b, ctx_b.a[l - 1], cw, False)
+        ops.conv_wgrad2(gz_a, ctx_a.a[l - 1], gz_b, ctx_b.a[l - 1], cw, False)
         if l > 1:
             # (no deferred slabs here: the two chains share one workspace and chain a's BatchNorm backward runs -- and uses it --
             # before chain b's would consume what chain b's conv left there)
@@ -355,12 +338,10 @@ def disc_backward_pair(ops, D: DiscNet, ctx_a, coef_a: float, ctx_b, coef_b: flo
     if R == 0:
         ga_a, ga_b = ops.lrelu_bwd(ga_a, ctx_a.a[0], D.slope), ops.lrelu_bwd(ga_b, ctx_b.a[0], D.slope)
     gz0_a, gz0_b = ga_a, ga_b
-    with ops.side(gz0_a, gz0_b):
-        ops.skinny_wgrad(gz0_a, ctx_a.x, D.conv0.dw, False)
-        ops.skinny_wgrad(gz0_b, ctx_b.x, D.conv0.dw, True)
+    ops.skinny_wgrad(gz0_a, ctx_a.x, D.conv0.dw, False)
+    ops.skinny_wgrad(gz0_b, ctx_b.x, D.conv0.dw, True)
     ops.col_sum(gz0_a, D.conv0.dbias, False)
     ops.col_sum(gz0_b, D.conv0.dbias, True)
-    ops.join()
 
 
 def disc_gradient_penalty(ops, D: DiscNet, xhat, lambd: float, update_running=True):
@@ -416,8 +397,7 @@ def disc_gp_second(ops, D: DiscNet, ctx, st, accumulate: bool, need_input_grad: 
         at, szt, sxz = ops.bn_tangent(ctx.z[l], zt, ctx.mean[l], ctx.invstd[l], bn.gamma, bn.beta, D.slope)
         zts.append(zt); ats.append(at); s_zt.append(szt); s_xhzt.append(sxz)
     # (4) joint reverse.  Head: t = sum_n lrelu'(h_n) * hdot_n  ->  dW_head = sum_n gh_n * at_R[n]
-    with ops.side():
-        ops.head_wgrad(ctx.gh, ats[R], D.head.dw, accumulate)
+    ops.head_wgrad(ctx.gh, ats[R], D.head.dw, accumulate)
     qa = None
     for l in range(R, 0, -1):
         cw, bn = D.blocks[l - 1]
@@ -425,20 +405,17 @@ def disc_gp_second(ops, D: DiscNet, ctx, st, accumulate: bool, need_input_grad: 
                                bn.gamma, bn.beta, D.slope, ctx.s_gy[l], ctx.s_gyxh[l],
                                s_zt[l], s_xhzt[l], bn.dgamma, bn.dbeta, accumulate)
         # dW = wgrad(pz, a_prev) + wgrad(gz1, at_prev): one launch, one split-K reduction
-        with ops.side(pz):
-            ops.conv_wgrad2(pz, ctx.a[l - 1], ctx.gz1[l], ats[l - 1], cw, accumulate)
+        ops.conv_wgrad2(pz, ctx.a[l - 1], ctx.gz1[l], ats[l - 1], cw, accumulate)
         qa = ops.conv_up(pz, cw) if l > 1 else ops.conv_up(pz, cw, ctx.a[0], D.slope)
     if R == 0:
         # no BatchNorm block: the penalty is piecewise constant in the first layer's parameters except through the head
         raise NotImplementedError("gradient penalty needs at least one Conv+BN block (in_size >= 32)")
     p0 = qa
-    with ops.side(p0, v):
-        done = ops.skinny_wgrad(p0, xhat, D.conv0.dw, accumulate, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
-        ops.skinny_wgrad(ctx.gz1[0], v, D.conv0.dw, True)
+    done = ops.skinny_wgrad(p0, xhat, D.conv0.dw, accumulate, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
+    ops.skinny_wgrad(ctx.gz1[0], v, D.conv0.dw, True)
     if not done:
         ops.col_sum(p0, D.conv0.dbias, accumulate)
     gx = ops.last_up(p0, D.conv0, None, False) if need_input_grad else None
-    ops.join()
     return gx
 
 
@@ -491,8 +468,7 @@ def _plain_backward(ops, D: PlainDiscNet, ctx, coef, wgrad, accumulate, need_inp
     else:
         gh = ops.head_grad(ctx.h, coef, D.last_slope)
     if wgrad:
-        with ops.side(gh):
-            ops.head_wgrad(gh, ctx.a[R], D.head.dw, accumulate)
+        ops.head_wgrad(gh, ctx.a[R], D.head.dw, accumulate)
         ops.vec_sum(gh, D.head.dbias, accumulate)
     # the head's data gradient meets the top layer's LeakyReLU: one elementwise pass over N x 4 x 4 x C
     gz = ops.lrelu_bwd(ops.head_bwd_data(gh, D.head), ctx.a[R], D.slope)
@@ -508,11 +484,9 @@ def _plain_backward(ops, D: PlainDiscNet, ctx, coef, wgrad, accumulate, need_inp
         if defer_w:
             ctx.gz_keep[l] = gz
         elif wgrad and partner is not None:
-            with ops.side(gz, partner.gz_keep[l]):
-                ops.conv_wgrad2(gz, ctx.a[l - 1], partner.gz_keep[l], partner.a[l - 1], cw, False)
+            ops.conv_wgrad2(gz, ctx.a[l - 1], partner.gz_keep[l], partner.a[l - 1], cw, False)
         elif wgrad:
-            with ops.side(gz):
-                ops.conv_wgrad(gz, ctx.a[l - 1], cw, accumulate)
+            ops.conv_wgrad(gz, ctx.a[l - 1], cw, accumulate)
         if l > 1:
             gz = ops.conv_up_mask(gz, cw, ctx.a[l - 1], D.slope, D.blocks[l - 2].dbias if wgrad else None, accumulate)
         else:
@@ -526,17 +500,15 @@ def _plain_backward(ops, D: PlainDiscNet, ctx, coef, wgrad, accumulate, need_inp
         ctx.gz_keep[0] = gz0
         ops.col_sum(gz0, D.conv0.dbias, accumulate)
     elif wgrad and partner is not None:
-        with ops.side(gz0, partner.gz_keep[0]):
-            done = ops.skinny_wgrad(gz0, ctx.x, D.conv0.dw, False, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
-            ops.skinny_wgrad(partner.gz_keep[0], partner.x, D.conv0.dw, True)
+        done = ops.skinny_wgrad(gz0, ctx.x, D.conv0.dw, False, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
+        ops.skinny_wgrad(partner.gz_keep[0], partner.x, D.conv0.dw, True)
         if not done:
             ops.col_sum(gz0, D.conv0.dbias, accumulate)
     elif wgrad:
         parts = [gz0[i * nx:(i + 1) * nx] for i in range(len(xs))] if len(xs) > 1 else [gz0]
-        with ops.side(gz0):
-            d0 = ops.skinny_wgrad(parts[0], xs[0], D.conv0.dw, accumulate, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
-            rest = [ops.skinny_wgrad(p, x, D.conv0.dw, True, dbias=D.conv0.dbias if d0 else None, dbias_accumulate=True)
-                    for p, x in zip(parts[1:], xs[1:])]
+        d0 = ops.skinny_wgrad(parts[0], xs[0], D.conv0.dw, accumulate, dbias=D.conv0.dbias, dbias_accumulate=accumulate)
+        rest = [ops.skinny_wgrad(p, x, D.conv0.dw, True, dbias=D.conv0.dbias if d0 else None, dbias_accumulate=True)
+                for p, x in zip(parts[1:], xs[1:])]
         if not d0:
             ops.col_sum(gz0, D.conv0.dbias, accumulate)
         else:
@@ -550,8 +522,6 @@ def _plain_backward(ops, D: PlainDiscNet, ctx, coef, wgrad, accumulate, need_inp
             gx, ctx.gx_parts = fused
     if need_input_grad and gx is None:
         gx = ops.last_up(gz0, D.conv0, None, False)
-    if wgrad:
-        ops.join()
     return gx
 
 
@@ -609,18 +579,14 @@ def _plain_gp_second(ops, D: PlainDiscNet, ctx, st, accumulate, need_input_grad)
     for l in range(1, R + 1):
         at = ops.conv_down_mask(at, D.blocks[l - 1], ctx.a[l], D.slope)
         ats.append(at)
-    with ops.side():
-        ops.head_wgrad(ctx.gh, ats[R], D.head.dw, accumulate)
+    ops.head_wgrad(ctx.gh, ats[R], D.head.dw, accumulate)
     for l in range(R, 0, -1):
-        with ops.side():
-            ops.conv_wgrad(ctx.gz1[l], ats[l - 1], D.blocks[l - 1], accumulate)
-    with ops.side(v):
-        ops.skinny_wgrad(ctx.gz1[0], v, D.conv0.dw, accumulate)
+        ops.conv_wgrad(ctx.gz1[l], ats[l - 1], D.blocks[l - 1], accumulate)
+    ops.skinny_wgrad(ctx.gz1[0], v, D.conv0.dw, accumulate)
     if not accumulate:
         for cw in D.convs():
             ops.zero_(cw.dbias)
     gx = ops.zero_(torch.empty_like(ctx.x)) if need_input_grad else None
-    ops.join()
     return gx
 
 
@@ -742,8 +708,7 @@ def gen_backward(ops, G: GenNet, ctx, gimg, accumulate: bool, need_input_grad: b
     R = len(G.blocks)
     if gzl is None:
         gzl = ops.tanh_bwd(gimg, ctx.img)
-    with ops.side(gzl):
-        ops.skinny_wgrad(ctx.a[R], gzl, G.last.dw, accumulate)
+    ops.skinny_wgrad(ctx.a[R], gzl, G.last.dw, accumulate)
     if gzl_parts is not None:
         ops.parts_chan_sum(gzl_parts, G.last.dbias, accumulate)
     else:
@@ -753,18 +718,14 @@ def gen_backward(ops, G: GenNet, ctx, gimg, accumulate: bool, need_input_grad: b
         cw, bn = G.blocks[l - 1]
         gz, _, _ = ops.bn_act_bwd(ctx.z[l], ga, ctx.mean[l], ctx.invstd[l], bn.gamma, bn.beta,
                                   G.slope, bn.dgamma, bn.dbeta, accumulate, keep_ga=False)
-        with ops.side(gz):
-            ops.conv_wgrad(ctx.a[l - 1], gz, cw, accumulate)
+        ops.conv_wgrad(ctx.a[l - 1], gz, cw, accumulate)
         # consumed by the BatchNorm backward of the layer below (next op): generator block l - 1, or G.0's BatchNorm
-        nxt = (ctx.z[l - 1], ctx.mean[l - 1], ctx.invstd[l - 1]) + \
-            ((G.blocks[l - 2][1].gamma, G.blocks[l - 2][1].beta) if l > 1 else (G.bn0.gamma, G.bn0.beta)) + (G.slope, 1)
-        ga = ops.conv_down(gz, cw, defer=1, bn_bwd=nxt)
+        ga = ops.conv_down(gz, cw, defer=1)
     gz0, _, _ = ops.bn_act_bwd(ctx.z[0], ga, ctx.mean[0], ctx.invstd[0], G.bn0.gamma, G.bn0.beta,
                                G.slope, G.bn0.dgamma, G.bn0.dbeta, accumulate, keep_ga=False)
     if not ops.g0_wgrad_deferred(ctx.noise, gz0, G.g0, accumulate):
         ops.g0_wgrad(ctx.noise, gz0, G.g0.dw, accumulate)
     gin = ops.g0_bwd_data(gz0, G.g0) if need_input_grad else None
-    ops.join()
     return gin
 
 
@@ -903,25 +864,20 @@ def disc_loss_grads_batched(ops, G, D: DiscNet, real, noise, grad_scale: float =
     loss = ops.mean_diff(out[n:], out[:n], 1.0)
     # backward: coefficient -1/n on the real half, +1/n on the fake half
     gh = torch.cat([ops.head_grad(hh[:n], -grad_scale / n, D.last_slope), ops.head_grad(hh[n:], grad_scale / n, D.last_slope)])
-    with ops.side(gh):
-        ops.head_wgrad(gh, acts[R], D.head.dw, False)
+    ops.head_wgrad(gh, acts[R], D.head.dw, False)
     ga = ops.head_bwd_data(gh, D.head)
     for l in range(R, 0, -1):
         cw, bn = D.blocks[l - 1]
         gz = ops.bn_act_bwd2(zs[l], ga, means[l], invstds[l], bn.gamma, bn.beta, D.slope, bn.dgamma, bn.dbeta, False)
-        with ops.side(gz):
-            ops.conv_wgrad(gz, acts[l - 1], cw, False)
-        ga = ops.conv_up(gz, cw, defer=2, bn_bwd=_bnb(zs, means, invstds, D.blocks, l - 1, D.slope, 2)) if l > 1 \
-            else ops.conv_up(gz, cw, acts[0], D.slope)
+        ops.conv_wgrad(gz, acts[l - 1], cw, False)
+        ga = ops.conv_up(gz, cw, defer=2) if l > 1 else ops.conv_up(gz, cw, acts[0], D.slope)
     gz0 = ga if R > 0 else ops.lrelu_bwd(ga, acts[0], D.slope)
-    with ops.side(gz0):
-        d0 = ops.skinny_wgrad(gz0[:n], xs[0], D.conv0.dw, False, dbias=D.conv0.dbias, dbias_accumulate=False)
-        d1 = ops.skinny_wgrad(gz0[n:], xs[1], D.conv0.dw, True, dbias=D.conv0.dbias if d0 else None, dbias_accumulate=True)
+    d0 = ops.skinny_wgrad(gz0[:n], xs[0], D.conv0.dw, False, dbias=D.conv0.dbias, dbias_accumulate=False)
+    d1 = ops.skinny_wgrad(gz0[n:], xs[1], D.conv0.dw, True, dbias=D.conv0.dbias if d0 else None, dbias_accumulate=True)
     if not d0:
         ops.col_sum(gz0, D.conv0.dbias, False)
     elif not d1:
         ops.col_sum(gz0[n:], D.conv0.dbias, True)
-    ops.join()
     return loss if next_noise is None else (loss, fake_next)
 
 

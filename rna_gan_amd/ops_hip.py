@@ -7,7 +7,6 @@ from __future__ import annotations
 import ctypes
 import os
 import weakref
-from contextlib import contextmanager
 
 import torch
 
@@ -154,15 +153,7 @@ class HipOps:
         # optional per-launch timing (bench.py roofline): list of (kernel family, algorithmic FLOPs,
         # start event, end event); events are recorded on the stream the kernels are enqueued on
         self.timing = None
-        # weight-gradient launches are forked onto a side stream (they are off the backward chain's critical
-        # path and MFMA-bound, so they co-run with the HBM-bound BatchNorm passes); own workspace; inputs are
-        # kept alive until join() so the caching allocator cannot hand their memory to the main stream early
-        self.side_stream = None
-        self._wsbuf_side = None
         self._ws_retired = []
-        self._in_side = False
-        self._keep = []
-        self.use_side = os.environ.get("RNAGAN_SIDE_STREAM", "0") != "0"
         # tanh backward / channel sums / squared norm of D's input gradient inside the kernel that writes it
         self.fuse_input_post = os.environ.get("RNAGAN_INPUT_POST", "1") != "0"
         self.pack_from_shadow = os.environ.get("RNAGAN_PACK_FROM_SHADOW", "1") != "0"
@@ -182,11 +173,6 @@ class HipOps:
         # kernel reduces them (RNAGAN_SPLIT_BN=0: conv + slab reduction + statistics + finisher + apply as separate launches)
         self.split_bn = os.environ.get("RNAGAN_SPLIT_BN", "1") != "0"
         self._split_bn_dp = None       # decided at the first use: fused split-K BatchNorm kernels only outside data-parallel runs
-        # data-gradient convs can also produce the BatchNorm-backward sums of the block they feed in their epilogue
-        # (rg_conv_*_bnbwd).  Built, exact, and NOT faster: the extra z read lands in the conv's tail, where every workgroup of
-        # the chip is in its epilogue at once (11.95-12.09 ms with the separate reduction pass vs 12.03-12.07 ms with the
-        # fused form, same box; the conv family drops from 0.408 to 0.382 of peak) -- off by default, RNAGAN_BWD_EPILOGUE=1
-        self.bwd_epilogue = os.environ.get("RNAGAN_BWD_EPILOGUE", "0") != "0"
         # fp32 storage: the stride-2 convs / transposed convs / weight gradients on the bf16 matrix cores from operands split ONCE
         # PER TENSOR into bf16 planes (rg_conv8f.hip): products per fp32 product -- 6 (every term down to 2^-24: fp32-grade, the
         # default), 3 (2^-16 per product), 0: the per-tile kernels of rg_generic.hip (f32mma option)
@@ -209,16 +195,10 @@ class HipOps:
         """Caller-owned workspace of the C ABI calls.  A buffer that is outgrown is RETIRED, not freed: captured HIP
         graphs replay launches that hold its address (growth is geometric, so the retired list stays short)."""
         nbytes = max(int(nbytes), 256)
-        if self._slabs_pending is not None and not self._in_side:
+        if self._slabs_pending is not None:
             # a deferred conv's split-K slabs live in this buffer until the BatchNorm op that was promised consumes them
             raise RuntimeError("rna_gan_amd: a conv launched with defer= left its split-K slabs in the workspace and another "
                                "op asked for the workspace before the BatchNorm op consumed them")
-        if self._in_side:
-            if self._wsbuf_side is None or self._wsbuf_side.numel() < nbytes:
-                if self._wsbuf_side is not None:
-                    self._ws_retired.append(self._wsbuf_side)
-                self._wsbuf_side = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=self.device)
-            return self._wsbuf_side
         if self._wsbuf is None or self._wsbuf.numel() < nbytes:
             if self._wsbuf is not None:
                 self._ws_retired.append(self._wsbuf)
@@ -258,31 +238,6 @@ class HipOps:
         if ns <= 1 or not self.lib.rg_slab_bn_supported(rows_out // groups, C, groups, ns):
             return 0
         return ns
-
-    @contextmanager
-    def side(self, *tensors):
-        """Run the enclosed ops on the side stream, ordered after everything enqueued so far on the
-        current stream.  ``tensors``: operands to keep alive until join()."""
-        if not self.use_side or self.timing is not None:
-            yield
-            return
-        if self.side_stream is None:
-            self.side_stream = torch.cuda.Stream(self.device)
-        main = torch.cuda.current_stream(self.device)
-        self.side_stream.wait_stream(main)
-        self._keep.extend(tensors)
-        self._in_side = True
-        try:
-            with torch.cuda.stream(self.side_stream):
-                yield
-        finally:
-            self._in_side = False
-
-    def join(self):
-        """Make the current stream wait for the side stream's work (before gradients are consumed)."""
-        if self.side_stream is not None and self.use_side:
-            torch.cuda.current_stream(self.device).wait_stream(self.side_stream)
-        self._keep.clear()
 
     def _timed(self, key, flops, thunk, cw=None):
         if self.timing is None:
@@ -412,30 +367,7 @@ class HipOps:
         rows = self.lib.rg_conv_stats_rows(up, N, Hl, Wl, O, I, self.dt, self.algo)
         return self._f32(rows, 2, C) if rows > 0 else None
 
-    def _bn_bwd_fused(self, up, y, cw_ptr, x, dims, bn_bwd, flops):
-        """Launch the conv with the consumer's BatchNorm-backward sums in its epilogue when this shape has that form; the
-        partial rows ride on the result as ``_rg_bwd_partials`` for bn_act_bwd / bn_act_bwd2.  True when launched."""
-        z, mean, invstd, gamma, beta, slope, groups = bn_bwd
-        N, Hl, Wl, O, I = dims
-        if (self.dt == RG_F32 or self.stat_reduce is not None or not self.bwd_epilogue or z.shape != y.shape or
-                z.dtype != y.dtype or not z.is_contiguous()):
-            return False
-        rows = int(self.lib.rg_conv_bnbwd_rows(up, N, Hl, Wl, O, I, groups, self.dt, self.algo))
-        if rows <= 0:
-            return False
-        C = y.shape[-1]
-        part = self._f32(rows, 2, C)
-        ws = self._ws(self.lib.rg_conv_workspace_bytes(up, N, Hl, Wl, O, I, self.dt, self.algo))
-        fn = self.lib.rg_conv_up_bnbwd if up else self.lib.rg_conv_down_bnbwd
-        a = (N, Hl, Wl, O, I) if up else (N, 2 * Hl, 2 * Wl, I, O)
-        self._timed("conv_fwd_dgrad", flops, lambda: check(
-            fn(_ptr(x), _ptr(cw_ptr), _ptr(y), *a, _ptr(z), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), float(slope),
-               int(groups), _ptr(part), self.dt, self.algo, _ptr(ws), ws.numel(), self.stream),
-            "rg_conv_up_bnbwd" if up else "rg_conv_down_bnbwd"))
-        y._rg_bwd_partials = (part, 4 if up else 1, groups)
-        return True
-
-    def conv_down(self, x, cw: ConvW, want_stats=False, defer=0, bn_bwd=None):
+    def conv_down(self, x, cw: ConvW, want_stats=False, defer=0):
         """Stride-2 conv.  want_stats: also return the per-tile column sums of y and y^2 written by the MFMA epilogue
         (None when this shape cannot produce them) for bn_forward(..., partials=...).
         defer = g > 0: the caller promises that the NEXT op on the result is the train-mode BatchNorm op (forward: bn_forward /
@@ -462,9 +394,6 @@ class HipOps:
                                   self.lib.rg_conv_slab_dtype(0, N, Hi // 2, Wi // 2, O, I, self.dt, self.algo))
             self._slabs_pending = y
             return (y, None) if want_stats else y
-        if bn_bwd is not None and not want_stats and self._bn_bwd_fused(
-                0, y, wdn, x, (N, Hi // 2, Wi // 2, O, I), bn_bwd, 2.0 * N * (Hi // 2) * (Wi // 2) * O * I * 16):
-            return y
         st = self._stats_buf(0, N, Hi // 2, Wi // 2, O, I, O) if want_stats else None
         ws = self._ws(self.lib.rg_conv_workspace_bytes(0, N, Hi // 2, Wi // 2, O, I, self.dt, self.algo))
         self._timed("conv_fwd_dgrad", 2.0 * N * (Hi // 2) * (Wi // 2) * O * I * 16, lambda: check(
@@ -472,7 +401,7 @@ class HipOps:
                                   self.algo, _ptr(ws), ws.numel(), self.stream), "rg_conv_down"), cw=cw)
         return (y, st) if want_stats else y
 
-    def conv_up(self, x, cw: ConvW, mask_act=None, slope=1.0, want_stats=False, defer=0, bn_bwd=None):
+    def conv_up(self, x, cw: ConvW, mask_act=None, slope=1.0, want_stats=False, defer=0):
         """Transposed conv; with mask_act (same shape as the result) the LeakyReLU backward
         ``y *= (mask_act > 0 ? 1 : slope)`` is applied in the kernel's epilogue.  want_stats, defer: as conv_down."""
         N, Ho, Wo, O = x.shape
@@ -500,9 +429,6 @@ class HipOps:
                                   self.lib.rg_conv_slab_dtype(1, N, Ho, Wo, O, I, self.dt, self.algo))
             self._slabs_pending = y
             return (y, None) if want_stats else y
-        if bn_bwd is not None and mask_act is None and not want_stats and self._bn_bwd_fused(
-                1, y, wup, x, (N, Ho, Wo, O, I), bn_bwd, 2.0 * N * Ho * Wo * O * I * 16):
-            return y
         assert mask_act is None or (mask_act.shape == y.shape and mask_act.dtype == y.dtype and mask_act.is_contiguous())
         st = self._stats_buf(1, N, Ho, Wo, O, I, I) if (want_stats and mask_act is None) else None
         ws = self._ws(self.lib.rg_conv_workspace_bytes(1, N, Ho, Wo, O, I, self.dt, self.algo))
@@ -752,7 +678,7 @@ class HipOps:
         """The weight gradient of a layer whose optimizer step follows immediately (cw.defer_slabs, set by the train_op runner):
         a split-K launch leaves its fp32 partial slabs in a buffer of the layer's own (cw.pending_slabs) and the reduction into
         dw is skipped -- rna_gan_amd.optim.Adam sums the slabs inside its step (rg_adam_step_slabs).  True when launched."""
-        if not cw.defer_slabs or self.dt == RG_F32 or self.stat_reduce is not None or self._in_side:
+        if not cw.defer_slabs or self.dt == RG_F32 or self.stat_reduce is not None:
             return False
         if accumulate or cw.pending_slabs is not None or cw.pending_wgrad is not None:
             raise RuntimeError("rna_gan_amd: a second weight-gradient contribution for a layer whose first one is still deferred "
@@ -1064,7 +990,7 @@ class HipOps:
         cw = self._skinny_defer.get(dw.data_ptr()) if self._skinny_defer else None
         if cw is not None and cw.pending_slabs is None and accumulate:
             cw = None          # the first contribution had no slab form (a small image) and wrote dw: this one adds to it
-        if cw is not None and self.dt != RG_F32 and self.stat_reduce is None and not self._in_side:
+        if cw is not None and self.dt != RG_F32 and self.stat_reduce is None:
             # the optimizer step follows at once (the train_op runner registered the layer): the per-workgroup partial gradients
             # stay in a buffer of the layer's own -- a second contribution (accumulate) behind the first one's -- and Adam sums them
             prev = cw.pending_slabs
@@ -1336,9 +1262,6 @@ class HipOps:
         sl = getattr(ga, "_rg_slabs", None)
         if sl is not None:
             return self._bn_act_bwd_slabs(z, ga, sl, 2, mean, invstd, gamma, beta, slope, dgamma, dbeta, accumulate, False)[0]
-        bp = getattr(ga, "_rg_bwd_partials", None)
-        if bp is not None and bp[2] == 2:
-            return self._bn_act_bwd_partials(z, ga, bp, 2, mean, invstd, gamma, beta, slope, dgamma, dbeta, accumulate)[0]
         gz = torch.empty_like(z)
         s_gy, s_gyxh = self._f32(2, C), self._f32(2, C)
         ws = self._ws(2 * self.lib.rg_colreduce_workspace_bytes(M, C, 2))
@@ -1371,20 +1294,6 @@ class HipOps:
         self._slabs_pending = None
         return gz, s_gy, s_gyxh
 
-    def _bn_act_bwd_partials(self, z, ga, bp, groups, mean, invstd, gamma, beta, slope, dgamma, dbeta, accumulate, out=None):
-        part, nblk, _ = bp
-        M2, C = self._mc(z)
-        M = M2 // groups
-        gz = out if out is not None else torch.empty_like(z)
-        s_gy, s_gyxh = (self._f32(C), self._f32(C)) if groups == 1 else (self._f32(groups, C), self._f32(groups, C))
-        ws = self._ws(groups * 32 * 2 * C * 4)
-        check(self.lib.rg_bn_act_bwd_partials(_ptr(part), part.shape[0] // groups, nblk, _ptr(z), _ptr(ga), _ptr(mean),
-                                              _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(gz), _ptr(s_gy), _ptr(s_gyxh),
-                                              _ptr(dgamma), _ptr(dbeta), int(accumulate), M, C, groups, float(slope), self.dt,
-                                              _ptr(ws), ws.numel(), self.stream), "rg_bn_act_bwd_partials")
-        del ga._rg_bwd_partials
-        return gz, s_gy, s_gyxh
-
     def bn_act_bwd(self, z, ga, mean, invstd, gamma, beta, slope: float, dgamma=None, dbeta=None,
                    accumulate: bool = False, out=None, keep_ga=True):
         """keep_ga: only meaningful when ga is still split-K slabs (conv_* with defer): also write the reduced ga tensor
@@ -1394,9 +1303,6 @@ class HipOps:
         if sl is not None:
             return self._bn_act_bwd_slabs(z, ga, sl, 1, mean, invstd, gamma, beta, slope, dgamma, dbeta, accumulate, keep_ga,
                                           out)
-        bp = getattr(ga, "_rg_bwd_partials", None)
-        if bp is not None and bp[2] == 1 and self.stat_reduce is None:
-            return self._bn_act_bwd_partials(z, ga, bp, 1, mean, invstd, gamma, beta, slope, dgamma, dbeta, accumulate, out)
         gz = out if out is not None else torch.empty_like(z)
         assert gz.shape == z.shape and gz.is_contiguous()
         s_gy, s_gyxh = self._f32(C), self._f32(C)
