@@ -285,7 +285,9 @@ int rg_linear_affine_act(const float* x, int ldx, const float* w, const void* wp
  * BatchNorm2d in TRAIN mode + LeakyReLU: forward, backward, forward-mode tangent and the joint
  * (double) backward needed by the gradient penalty (K6/K7).  z, a, g* are [M][C] views of NHWC
  * tensors (M = N*H*W).  All column reductions are two-stage and deterministic; `ws` must hold
- * rg_colreduce_workspace_bytes(M, C, nq) bytes (nq = number of sums, <= 3).
+ * rg_colreduce_workspace_bytes(M, C, nq) bytes (nq = number of sums, <= 3).  Every entry point below that takes `ws` checks
+ * the size it documents BEFORE any launch and returns RG_EWORKSPACE for one byte less -- also where the form it takes for
+ * this shape needs less or none (rg_bn_forward's single-launch form; a partial-row finish that stays single-level).
  * ------------------------------------------------------------------------------------------- */
 size_t rg_colreduce_workspace_bytes(int M, int C, int nq);
 
@@ -311,7 +313,7 @@ int rg_bn_forward(const void* z, int M, int C, float eps, float momentum, const 
 int rg_bn_forward_partials(const float* partial, int G, const void* z, int M, int C, float eps, float momentum,
                            const float* gamma, const float* beta, float slope, float* mean, float* invstd,
                            float* running_mean, float* running_var, int64_t* num_batches_tracked, void* a, int dtype,
-                           void* ws, size_t ws_bytes, void* stream);     /* ws: 32 * 2 * C floats (two-level finish) */
+                           void* ws, size_t ws_bytes, void* stream);     /* ws: 32 * 2 * C floats (two-level finish); less is refused */
 int rg_bn_stats_finalize(const void* z, int M, int C, float eps, float momentum, float* mean, float* invstd,
                          float* running_mean, float* running_var, int64_t* num_batches_tracked, int dtype, void* ws,
                          size_t ws_bytes, void* stream);
@@ -323,7 +325,8 @@ int rg_bn_act(const void* z, const float* mean, const float* invstd, const float
 int rg_bn_act_bwd(const void* z, const void* ga, const float* mean, const float* invstd, const float* gamma,
                   const float* beta, void* gz, float* s_gy, float* s_gyxh, float* dgamma, float* dbeta,
                   int accumulate, int M, int C, float slope, int dtype, void* ws, size_t ws_bytes, void* stream);
-/* mean / invstd (+ running statistics) from the conv epilogue's column sums, without the normalisation pass. */
+/* mean / invstd (+ running statistics) from the conv epilogue's column sums, without the normalisation pass.
+ * ws: 32 * 2 * C floats (the staging area of the two-level finish, G > 512 and C % 8 == 0); less is refused. */
 int rg_bn_finalize_partials(const float* partial, int G, int M, int C, float eps, float momentum, float* mean,
                             float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, void* ws,
                             size_t ws_bytes, void* stream);
@@ -413,7 +416,9 @@ int rg_bn_act_bwd_slabs(const void* slab, int nsplit, size_t slab_stride, int sl
  * rg_bn_forward_partials (partial != NULL: 2*G rows [.][2][C] laid out [nblk][2 halves][G/nblk] -- nblk = 1 for
  * rg_conv_down's row-tile order, 4 for rg_conv_up's class-major order) or rg_bn_forward (partial == NULL) on the first half,
  * then on the second (running statistics and num_batches_tracked updated in that order); rg_bn_act_bwd_g2 = rg_bn_act_bwd on both
- * halves with dgamma / dbeta summed.  Workspace: twice rg_colreduce_workspace_bytes(M, C, 2). */
+ * halves with dgamma / dbeta summed.  Workspace: twice rg_colreduce_workspace_bytes(M, C, 2) for rg_bn_act_bwd_g2 and for
+ * rg_bn_forward_g2 without partial rows; 2 * 32 * 2 * C floats for rg_bn_finalize_partials_g2 and for rg_bn_forward_g2 with
+ * partial rows.  Less is refused (RG_EWORKSPACE). */
 int rg_bn_finalize_partials_g2(const float* partial, int G, int nblk, int M, int C, float eps, float momentum, float* mean,
                                float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked,
                                void* ws, size_t ws_bytes, void* stream);

@@ -190,7 +190,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES
-ABI_VERSION = 613
+ABI_VERSION = 614
 
 _libs = {}
 LIB_PATH_F16 = os.path.join(_HERE, "librnagan_hip_f16.so")

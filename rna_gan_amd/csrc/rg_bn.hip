@@ -716,9 +716,30 @@ extern "C" size_t rg_colreduce_workspace_bytes(int M, int C, int nq) {
   return rg_align_up((size_t)max_gy(M, C) * (nq < 1 ? 1 : nq) * C * sizeof(float), 256) + (size_t)5 * C * sizeof(float);
 }
 
+// The header's contract for every column reduction: `ws` holds `times` x rg_colreduce_workspace_bytes(M, C, nq).  Checked as
+// promised, before any launch -- row_reduce_g's own check is against what ONE element type's plan needs, which is less: a caller
+// that sized its workspace by that smaller figure would pass with one storage type and be refused with the other.
+static inline int require_colws(const char* name, const void* ws, size_t ws_bytes, int M, int C, int nq, int times) {
+  const size_t need = (size_t)times * rg_colreduce_workspace_bytes(M, C, nq);
+  RG_REQUIRE(ws && ws_bytes >= need, RG_EWORKSPACE, "%s: workspace %zu < %zu", name, ws_bytes, need);
+  return RG_OK;
+}
+#define RG_REQUIRE_COLWS(name, times, nq)                                              \
+  do {                                                                                 \
+    if (int rc__ = require_colws(name, ws, ws_bytes, M, C, nq, times)) return rc__;    \
+  } while (0)
+// The partial-row finishers: `ws` holds the staging area of the two-level finish, `groups` x 32 x 2 x C floats, whether or not
+// this G and C take the two-level form (no quiet change of path with the size of the workspace).
+static inline int require_stagews(const char* name, const void* ws, size_t ws_bytes, int C, int groups) {
+  const size_t need = (size_t)groups * 32 * 2 * C * sizeof(float);
+  RG_REQUIRE(ws && ws_bytes >= need, RG_EWORKSPACE, "%s: workspace %zu < %zu", name, ws_bytes, need);
+  return RG_OK;
+}
+
 extern "C" int rg_bn_stats(const void* z, float* sum, float* sumsq, int M, int C, int dtype, void* ws, size_t ws_bytes,
                            void* stream) {
   RG_REQUIRE(z && sum && sumsq && M > 0 && C > 0, RG_EINVAL, "bn_stats: bad args");
+  RG_REQUIRE_COLWS("bn_stats", 1, 2);
   RG_DISPATCH_DTYPE(dtype, T, {
     return (row_reduce<2, T, StatsF>("bn_stats", M, C, ws, ws_bytes, rg_stream(stream), Store2Fin{sum, sumsq},
                                      (const T*)z, C));
@@ -729,6 +750,7 @@ extern "C" int rg_bn_stats_finalize(const void* z, int M, int C, float eps, floa
                                     float* running_mean, float* running_var, int64_t* num_batches_tracked, int dtype,
                                     void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(z && mean && invstd && M > 0 && C > 0, RG_EINVAL, "bn_stats_finalize: bad args");
+  RG_REQUIRE_COLWS("bn_stats_finalize", 1, 2);
   StatsFinalizeFin fin{(float)M, eps, momentum, mean, invstd, running_mean, running_var,
                        running_mean ? num_batches_tracked : nullptr};
   RG_DISPATCH_DTYPE(dtype, T, {
@@ -740,6 +762,7 @@ extern "C" int rg_bn_forward(const void* z, int M, int C, float eps, float momen
                              float slope, float* mean, float* invstd, float* running_mean, float* running_var,
                              int64_t* num_batches_tracked, void* a, int dtype, void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(z && a && mean && invstd && gamma && beta && M > 0 && C > 0, RG_EINVAL, "bn_forward: bad args");
+  RG_REQUIRE_COLWS("bn_forward", 1, 2);
   StatsFinalizeFin fin{(float)M, eps, momentum, mean, invstd, running_mean, running_var,
                        running_mean ? num_batches_tracked : nullptr};
   BNC p{mean, invstd, gamma, beta, slope};
@@ -761,13 +784,14 @@ extern "C" int rg_bn_forward_partials(const float* partial, int G, const void* z
                                       int dtype, void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(partial && G > 0 && z && a && mean && invstd && gamma && beta && M > 0 && C > 0, RG_EINVAL,
              "bn_forward_partials: bad args");
+  if (int rc = require_stagews("bn_forward_partials", ws, ws_bytes, C, 1)) return rc;
   StatsFinalizeFin fin{(float)M, eps, momentum, mean, invstd, running_mean, running_var,
                        running_mean ? num_batches_tracked : nullptr};
   BNC p{mean, invstd, gamma, beta, slope};
   hipStream_t st = rg_stream(stream);
   // many partial rows (big layers: one per row tile and wave row): two levels, 32 slices first
   constexpr int SLICES = 32;
-  if (G > 512 && C % 8 == 0 && ws && ws_bytes >= (size_t)SLICES * 2 * C * sizeof(float)) {
+  if (G > 512 && C % 8 == 0) {
     float* stage = (float*)ws;
     hipLaunchKernelGGL((colfinish_wide_kernel<2, SliceFin>), dim3(C / 8, SLICES), dim3(256), 0, st, SliceFin{stage, C},
                        partial, C, G);
@@ -787,11 +811,12 @@ extern "C" int rg_bn_finalize_partials(const float* partial, int G, int M, int C
                                        float* invstd, float* running_mean, float* running_var,
                                        int64_t* num_batches_tracked, void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(partial && G > 0 && mean && invstd && M > 0 && C > 0, RG_EINVAL, "bn_finalize_partials: bad args");
+  if (int rc = require_stagews("bn_finalize_partials", ws, ws_bytes, C, 1)) return rc;
   StatsFinalizeFin fin{(float)M, eps, momentum, mean, invstd, running_mean, running_var,
                        running_mean ? num_batches_tracked : nullptr};
   hipStream_t st = rg_stream(stream);
   constexpr int SLICES = 32;
-  if (G > 512 && C % 8 == 0 && ws && ws_bytes >= (size_t)SLICES * 2 * C * sizeof(float)) {
+  if (G > 512 && C % 8 == 0) {
     float* stage = (float*)ws;
     hipLaunchKernelGGL((colfinish_wide_kernel<2, SliceFin>), dim3(C / 8, SLICES), dim3(256), 0, st, SliceFin{stage, C},
                        partial, C, G);
@@ -813,7 +838,8 @@ static int finalize_partials_g2(const char* name, const float* partial, int G, i
                                 size_t ws_bytes, hipStream_t st) {
   constexpr int SLICES = 32;
   RG_REQUIRE(nblk >= 1 && G % nblk == 0, RG_EINVAL, "%s: partial rows %d not a multiple of %d blocks", name, G, nblk);
-  if (G > 512 && C % 8 == 0 && ws && ws_bytes >= (size_t)2 * SLICES * 2 * C * sizeof(float)) {
+  if (int rc = require_stagews(name, ws, ws_bytes, C, 2)) return rc;
+  if (G > 512 && C % 8 == 0) {
     float* stage = (float*)ws;
     hipLaunchKernelGGL((colfinish_wide_kernel<2, SliceFin>), dim3(C / 8, SLICES, 2), dim3(256), 0, st,
                        SliceFin{stage, C, SLICES}, partial, C, G, nblk);
@@ -856,6 +882,7 @@ extern "C" int rg_bn_forward_g2(const float* partial, int G, int nblk, const voi
       return (row_apply_g<T, BnActF>("bn_forward_g2", 2, M, C, st, (const T*)z, (T*)a, p, C, gs));
     })
   }
+  RG_REQUIRE_COLWS("bn_forward_g2", 2, 2);
   RG_DISPATCH_DTYPE(dtype, T, {
     int rc = row_reduce_g<2, T, StatsF>("bn_forward_g2", 2, M, C, ws, ws_bytes, st, fin, (const T*)z, C, gs);
     if (rc) return rc;
@@ -871,6 +898,7 @@ extern "C" int rg_bn_act_bwd_g2(const void* z, const void* ga, const float* mean
                                 void* stream) {
   RG_REQUIRE(z && ga && gz && s_gy && s_gyxh && M > 0 && C > 0, RG_EINVAL, "bn_act_bwd_g2: bad args");
   RG_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), RG_EINVAL, "bn_act_bwd_g2: dgamma/dbeta must come together");
+  RG_REQUIRE_COLWS("bn_act_bwd_g2", 2, 2);
   BNC p{mean, invstd, gamma, beta, slope};
   hipStream_t st = rg_stream(stream);
   const size_t gs = (size_t)M * C;
@@ -909,6 +937,7 @@ extern "C" int rg_bn_act_bwd(const void* z, const void* ga, const float* mean, c
                              void* stream) {
   RG_REQUIRE(z && ga && gz && s_gy && s_gyxh && M > 0 && C > 0, RG_EINVAL, "bn_act_bwd: bad args");
   RG_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), RG_EINVAL, "bn_act_bwd: dgamma/dbeta must come together");
+  RG_REQUIRE_COLWS("bn_act_bwd", 1, 2);
   BNC p{mean, invstd, gamma, beta, slope};
   hipStream_t st = rg_stream(stream);
   RG_DISPATCH_DTYPE(dtype, T, {
@@ -930,6 +959,7 @@ extern "C" int rg_bn_tangent(const void* z, const void* zt, const float* mean, c
                              const float* beta, void* at, float* s_zt, float* s_xhzt, int M, int C, float slope,
                              int dtype, void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(z && zt && at && s_zt && s_xhzt && M > 0 && C > 0, RG_EINVAL, "bn_tangent: bad args");
+  RG_REQUIRE_COLWS("bn_tangent", 1, 2);
   BNC p{mean, invstd, gamma, beta, slope};
   hipStream_t st = rg_stream(stream);
   RG_DISPATCH_DTYPE(dtype, T, {
@@ -983,6 +1013,7 @@ extern "C" int rg_bn_bwd_sums(const void* z, const void* ga, const float* mean, 
                               const float* beta, float* s_gy, float* s_gyxh, int M, int C, float slope, int dtype, void* ws,
                               size_t ws_bytes, void* stream) {
   RG_REQUIRE(z && ga && s_gy && s_gyxh && M > 0 && C > 0, RG_EINVAL, "bn_bwd_sums: bad args");
+  RG_REQUIRE_COLWS("bn_bwd_sums", 1, 2);
   BNC p{mean, invstd, gamma, beta, slope};
   RG_DISPATCH_DTYPE(dtype, T, {
     return (row_reduce<2, T, BwdRedF>("bn_bwd_sums", M, C, ws, ws_bytes, rg_stream(stream), Store2Fin{s_gy, s_gyxh},
@@ -1003,6 +1034,7 @@ extern "C" int rg_bn_tangent_sums(const void* z, const void* zt, const float* me
                                   const float* gamma, const float* beta, float* s_zt, float* s_xhzt, int M, int C,
                                   float slope, int dtype, void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(z && zt && s_zt && s_xhzt && M > 0 && C > 0, RG_EINVAL, "bn_tangent_sums: bad args");
+  RG_REQUIRE_COLWS("bn_tangent_sums", 1, 2);
   BNC p{mean, invstd, gamma, beta, slope};
   RG_DISPATCH_DTYPE(dtype, T, {
     return (row_reduce<2, T, TanRedF>("bn_tangent_sums", M, C, ws, ws_bytes, rg_stream(stream), Store2Fin{s_zt, s_xhzt},
@@ -1023,6 +1055,7 @@ extern "C" int rg_bn_dbl_sums(const void* z, const void* qa, const void* zt, con
                               const float* invstd, const float* gamma, const float* beta, float* raw3, int M, int C,
                               float slope, int dtype, void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(z && zt && ga1 && raw3 && M > 0 && C > 0, RG_EINVAL, "bn_dbl_sums: bad args");
+  RG_REQUIRE_COLWS("bn_dbl_sums", 1, 3);
   BNC p{mean, invstd, gamma, beta, slope};
   RG_DISPATCH_DTYPE(dtype, T, {
     return (row_reduce<3, T, DblRedF>("bn_dbl_sums", M, C, ws, ws_bytes, rg_stream(stream), Store3Fin{raw3, C},
@@ -1055,6 +1088,7 @@ extern "C" int rg_bn_dbl_apply(const void* z, const void* qa, const void* zt, co
 extern "C" int rg_col_sum(const void* g, float* out, int M, int C, int dtype, int accumulate, void* ws, size_t ws_bytes,
                           void* stream) {
   RG_REQUIRE(g && out && M > 0 && C > 0, RG_EINVAL, "col_sum: bad args");
+  RG_REQUIRE_COLWS("col_sum", 1, 1);
   RG_DISPATCH_DTYPE(dtype, T, {
     return (row_reduce<1, T, ColSumF>("col_sum", M, C, ws, ws_bytes, rg_stream(stream), AccFin{out, accumulate},
                                       (const T*)g, C));

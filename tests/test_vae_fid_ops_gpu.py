@@ -23,12 +23,11 @@ import torch
 
 import vae_fid_refs as R
 from both_builds import fp16_twin
+from guarded import DEV, SBITS, Guarded, _assert_sentinel, _out
 from vae_fid_refs import SENTINEL, U32, bits, ceil64
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NAN = float("nan")
-SBITS = 0x5e59e2d3                                  # bits of SENTINEL
 
 
 class _Env:
@@ -55,31 +54,6 @@ def _ptr(t):
 
 def _dev(t, dtype=torch.float32):
     return None if t is None else t.to(dtype).to(DEV).contiguous()
-
-
-class Guarded:
-    """A tensor in the middle of a larger allocation filled with `fill` (NaN around operands, SENTINEL around outputs).  The
-    offsets keep 256-byte alignment.  `after` is sized by the caller to cover the farthest overrun it wants to see."""
-
-    def __init__(self, t, fill, before=128, after=4096):
-        n = t.numel()
-        self.flat = torch.full((before + n + after,), fill, dtype=t.dtype, device=DEV)
-        self.flat[before:before + n] = t.reshape(-1).to(DEV)
-        self.t = self.flat[before:before + n].view(t.shape)
-        self.before, self.n = before, n
-
-    def surroundings_keep(self, pattern):
-        head, tail = self.flat[:self.before], self.flat[self.before + self.n:]
-        return bool((bits(head) == pattern).all()) and bool((bits(tail) == pattern).all())
-
-
-def _out(shape, after=4096):
-    return Guarded(torch.full(shape, SENTINEL, dtype=torch.float32), SENTINEL, after=after)
-
-
-def _assert_sentinel(t, what):
-    assert bool((bits(t) == SBITS).all()), "%s: %d elements that must stay untouched were written" % (
-        what, int((bits(t) != SBITS).sum()))
 
 
 def _assert_pos_zero(t, what):
