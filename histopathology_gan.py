@@ -74,6 +74,9 @@ EXTRA_FLAGS = [
                                       "with a non-finite gradient is skipped and the scale halved; it grows after clean steps)"),
     ("--critic_batchnorm", int, 1, "0 = BatchNorm-free critic (DCGANDiscriminator(batchnorm=False): biased convs, what a WGAN-GP "
                                    "recipe uses -- the penalty is per input and train-mode BatchNorm couples the batch)"),
+    ("--g_ema", float, 0.0, "decay in [0, 1) of an exponential moving average of the generator's weights, kept on the device "
+                            "inside the optimizer step and saved / sampled next to the generator (0 = off)"),
+    ("--g_ema_warmup", int, 1, "1 = the average's decay is min(g_ema, (1 + t) / (10 + t)) at generator step t, 0 = constant"),
 ]
 
 
@@ -106,7 +109,12 @@ def parse_args():
     for flag, typ, default, text in REFERENCE_FLAGS + EXTRA_FLAGS:
         ap.add_argument(flag, type=typ, default=default, help=text)
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic tiles / RNA rows")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not 0.0 <= args.g_ema < 1.0:
+        ap.error("--g_ema must be in [0, 1)")
+    if args.g_ema_warmup not in (0, 1):
+        ap.error("--g_ema_warmup must be 0 or 1")
+    return args
 
 
 def main():
@@ -196,7 +204,8 @@ def main():
     epochs = args.num_epochs if args.num_epochs is not None else 5
     print("Device: {}".format(device)); print("Epochs: {}".format(epochs))
     trainer = P.Trainer(gan_network, losses, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
-                        recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling)
+                        recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,
+                        ema_decay=args.g_ema if args.g_ema > 0.0 else None, ema_warmup=bool(args.g_ema_warmup))
     if args.checkpoint is not None:
         trainer.load_model(load_path=args.checkpoint)
     for loss in losses:                                   # identical frozen encoders on every rank (rank 0's)

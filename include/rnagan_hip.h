@@ -569,6 +569,15 @@ int rg_adam_hyper_dev2(int* step_dev, double lr, double beta1, double beta2, dou
 #define RG_AMP_STATE_INTS 12
 int rg_adam_hyper_dev3(int* step_dev, double lr, double beta1, double beta2, double eps, double weight_decay,
                        const int* amp_state, int slot, float* hyper, void* stream);
+/* Exponential moving average of a parameter buffer (rna_gan_amd.ema.ParamEMA: the averaged generator), one launch behind the
+ * Adam launches of a step:
+ *   e[i] <- e[i] + omd * (p[i] - e[i]),  omd = 1.f - d, every operation a separately rounded fp32 operation in exactly that
+ * order.  d = decay when step_dev == NULL; otherwise d = fminf(decay, (1.f + (float)t) / (10.f + (float)t)) with t = *step_dev
+ * read on the device (Adam's 1-based step counter AFTER this step's rg_adam_hyper_dev* launch): the usual warm-up, so that the
+ * average forgets its initial value quickly.  Returns at once, touching nothing, when hyper != NULL and hyper[9] != 0 (the skip
+ * word above).  p is only read.  p, e: 16-byte aligned fp32, any n.  0 <= decay < 1, else RG_EINVAL (as for a NULL or
+ * misaligned buffer with n > 0) and nothing is launched.  No 16-bit type is involved: both builds behave identically. */
+int rg_ema_update(const float* p, float* e, size_t n, float decay, const int* step_dev, const float* hyper, void* stream);
 /* OR "any non-finite value" into *flag: nseg <= 32 segments (HOST arrays) of seg_n[i] elements at seg_ptr[i], fp32 or this build's
  * 16-bit type by seg_dtype[i] (element-aligned; any length).  Exponent-mask test on the raw bits (fp32 0x7f800000, fp16 0x7c00,
  * bf16 0x7f80), wave-level OR, one atomic per wave that found something; nothing is written otherwise. */

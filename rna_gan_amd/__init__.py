@@ -7,7 +7,8 @@ from .losses import (WassersteinDiscriminatorLoss, WassersteinDiscriminatorLossV
                      WassersteinGradientPenaltyVAE)
 from .trainer import Trainer  # noqa: F401
 from .optim import Adam  # noqa: F401
+from .ema import ParamEMA  # noqa: F401
 
-__all__ = ["DCGANGenerator", "DCGANUpGenerator", "DCGANDiscriminator", "Generator", "Discriminator", "betaVAE", "Trainer", "Adam",
+__all__ = ["DCGANGenerator", "DCGANUpGenerator", "DCGANDiscriminator", "Generator", "Discriminator", "betaVAE", "Trainer", "Adam", "ParamEMA",
            "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss", "WassersteinGradientPenalty",
            "WassersteinGeneratorLossVAE", "WassersteinDiscriminatorLossVAE", "WassersteinGradientPenaltyVAE"]

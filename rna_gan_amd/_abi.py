@@ -120,6 +120,7 @@ PROTOTYPES = {
     "rg_latent_apply": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "rg_adam_step_dev": (_i, [_p, _p, _p, _p, _z, _p, _p, _p, _p]),
     "rg_adam_step_slabs": (_i, [_p, _p, _p, _p, _z, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "rg_ema_update": (_i, [_p, _p, _z, _f, _p, _p, _p]),
     "rg_interp_dev": (_i, [_p, _p, _p, _z, _p, _p]),
     "rg_adam_hyper_dev": (_i, [_p, _d, _d, _d, _d, _d, _p, _p]),
     "rg_adam_hyper_dev2": (_i, [_p, _d, _d, _d, _d, _d, _d, _p, _p]),
@@ -190,7 +191,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES
-ABI_VERSION = 614
+ABI_VERSION = 615
 
 _libs = {}
 LIB_PATH_F16 = os.path.join(_HERE, "librnagan_hip_f16.so")

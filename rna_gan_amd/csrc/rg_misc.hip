@@ -128,6 +128,33 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
   }
 }
 
+// ---- exponential moving average of a parameter buffer (rna_gan_amd.ema): e <- e + (1 - d) * (p - e), three separately
+// rounded fp32 operations (the build has contraction off).  A pure stream of 12 B per element behind the Adam launches of
+// the same step: p was just written (plain load), e is touched once per step (non-temporal, like m and v above).  The decay
+// is a kernel argument; with step_dev it is warmed up from Adam's device-side step counter, so the launch replays from a
+// captured graph; hyper[9] is the skip word of a step that dynamic loss scaling skipped.
+constexpr unsigned EMA_MAX_BLOCKS = 2048;                  // 256 CUs x 8 workgroups: the rest is the grid-stride loop
+__global__ __launch_bounds__(256) void ema_kernel(const float* __restrict__ p, float* __restrict__ e, size_t n, float decay,
+                                                  const int* __restrict__ step_dev, const float* __restrict__ hyper) {
+  if (hyper != nullptr && hyper[9] != 0.f) return;         // skipped step (rg_adam_hyper_dev3)
+  float d = decay;
+  if (step_dev != nullptr) {
+    const float t = (float)step_dev[0];
+    d = fminf(decay, (1.f + t) / (10.f + t));
+  }
+  const float omd = 1.f - d;
+  const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
+    const size_t i = q * 4;
+    const float4 P = *(const float4*)(p + i);
+    float4 E = nt_ld4(e + i);
+    E.x = E.x + omd * (P.x - E.x); E.y = E.y + omd * (P.y - E.y); E.z = E.z + omd * (P.z - E.z); E.w = E.w + omd * (P.w - E.w);
+    nt_st4(e + i, E);
+  }
+  const size_t t = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // tail
+  if (t < n) e[t] = e[t] + omd * (p[t] - e[t]);
+}
+
 // ---- Adam over a flat buffer cut into SEGMENTS, some of whose gradients are still split-K partial slabs of their weight-
 // gradient launch ([nsplit][n] fp32, rg_conv_wgrad_slabs): the step sums them itself, in slab order, instead of reading a
 // reduced gradient -- the reduction launches of a backward pass (5-6 per pass at ~12 us: bandwidth-bound, 67 MB of slabs each)
@@ -662,6 +689,19 @@ extern "C" int rg_adam_step_dev(float* p, const float* g, float* m, float* v, si
   else if (sh) hipLaunchKernelGGL((adam_dev_kernel<false, true>), grid, block, 0, st, p, g, m, v, hyper, sh, gw, n);
   else hipLaunchKernelGGL((adam_dev_kernel<false, false>), grid, block, 0, st, p, g, m, v, hyper, sh, gw, n);
   RG_LAUNCH_CHECK("adam_step_dev");
+  return RG_OK;
+}
+extern "C" int rg_ema_update(const float* p, float* e, size_t n, float decay, const int* step_dev, const float* hyper,
+                             void* stream) {
+  RG_REQUIRE(decay >= 0.f && decay < 1.f, RG_EINVAL, "ema_update: decay %g is outside [0, 1)", (double)decay);
+  if (n == 0) return RG_OK;
+  RG_REQUIRE(p && e, RG_EINVAL, "ema_update: null buffer");
+  RG_REQUIRE(aligned16(p) && aligned16(e), RG_EINVAL, "ema_update: 16-byte alignment");
+  size_t blocks = (n / 4 + 255) / 256;
+  if (blocks > EMA_MAX_BLOCKS) blocks = EMA_MAX_BLOCKS;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, rg_stream(stream), p, e, n, decay, step_dev, hyper);
+  RG_LAUNCH_CHECK("ema_update");
   return RG_OK;
 }
 // Adam over [p, p + n) cut into nseg consecutive segments (seg_off / seg_n in elements, covering the range in order; every

@@ -34,6 +34,7 @@ class Adam(torch.optim.Adam):
         self._host_steps = 0       # number of steps enqueued/replayed so far (mirror of *_step_dev)
         self.buf_gen = 0           # bumped whenever the moment / step buffers are re-allocated (part of the graph keys)
         self.grad_wire = None      # data parallel, bf16 wire: the all-reduced bf16 gradient buffer to step from
+        self._ema = None           # rna_gan_amd.ema.ParamEMA kept by one more launch of step() (attach_ema)
 
     def bind(self, module, fuse_linear_wgrad=False):
         """Tell the optimizer which HIP module owns its parameters (done by the Trainer).  The fused step updates the
@@ -56,6 +57,30 @@ class Adam(torch.optim.Adam):
             if hasattr(module, "_trt"):
                 module._trt = None                 # the training runtime reads the flag when it is built
         return self
+
+    def attach_ema(self, ema):
+        """Keep ``ema`` (rna_gan_amd.ema.ParamEMA of the bound module) current: one rg_ema_update launch behind the Adam
+        launches of every step().  The launch changes what a captured step graph holds, so buf_gen (part of the graph keys)
+        is bumped: a graph captured without it is never replayed with it."""
+        if self._module is None or ema.source is not self._module:
+            raise ValueError("rna_gan_amd.optim.Adam: attach_ema needs an optimizer bound to the module the ParamEMA averages")
+        if self._ema is not None and self._ema is not ema:
+            raise RuntimeError("rna_gan_amd.optim.Adam: another ParamEMA is attached (detach_ema() first)")
+        from . import dist as D_
+        D_.flush()                 # a pending data-parallel step of this optimizer was armed without the launch
+        ema._attach(self)
+        self._ema = ema
+        self.buf_gen += 1
+        return ema
+
+    def detach_ema(self):
+        ema, self._ema = self._ema, None
+        if ema is not None:
+            from . import dist as D_
+            D_.flush()
+            ema._detach()
+            self.buf_gen += 1
+        return ema
 
     def _ensure(self):
         if self._module is None:
@@ -80,6 +105,8 @@ class Adam(torch.optim.Adam):
             self._hyper = torch.zeros(12, dtype=torch.float32, device=flat.data.device)
             self._flat_id = flat
             self.buf_gen += 1
+        if self._ema is not None and not torch.cuda.is_current_stream_capturing() and self._ema._rehomed():
+            self.buf_gen += 1      # the live module or the averaged twin moved: graphs holding the old addresses are not replayed
         return flat
 
     def _sync_step_state(self):
@@ -134,6 +161,8 @@ class Adam(torch.optim.Adam):
     def note_replayed(self):
         """A captured graph containing one step of this optimizer was replayed."""
         self._host_steps += 1
+        if self._ema is not None:
+            self._ema.module.weights_changed()     # the replayed rg_ema_update moved the twin's masters (no shadow written)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -303,6 +332,9 @@ class Adam(torch.optim.Adam):
             amp.hyper(lib, self._module, self._step_dev, g, self._hyper, stream)
         for fn in launches:
             fn()
+        if self._ema is not None:
+            # the average of the parameters just written: same stream, same step counter (warm-up) and skip word
+            self._ema._launch(lib, self._hyper, self._step_dev, stream)
         if amp is not None:
             amp.update(lib, self._module, stream)
         if not torch.cuda.is_current_stream_capturing():

@@ -15,6 +15,9 @@ and absent from the reference tree; behaviour follows SURVEY.md Appendix A:
   * checkpoint dict keys: epoch, loss_information, loss_objects, metric_objects, loss_logs,
     metric_logs, <model>, optimizer_<model>.
 
+Extra (``ema_decay``): an exponential moving average of the generator's weights (rna_gan_amd.ema), exposed as
+``generator_ema``, sampled to ``epoch<e+1>_generator_ema.png`` and saved under the extra keys generator_ema / ema_information.
+
 Data parallel: one process per GPU; rank 0's parameters are broadcast at start, gradients are
 all-reduced inside the losses, only rank 0 writes checkpoints / images.
 """
@@ -35,7 +38,7 @@ class Trainer:
     def __init__(self, models, losses_list, metrics_list=None, device=torch.device("cuda:0"), ncritic=1, epochs=5,
                  sample_size=8, checkpoints="./model/gan", retain_checkpoints=5, recon="./images", log_dir=None,
                  test_noise=None, nrow=8, precision="bf16", prefetch=True, loss_scaling="static", loss_scaling_args=None,
-                 **kwargs):
+                 ema_decay=None, ema_warmup=True, **kwargs):
         self.device = torch.device(device)
         self.prefetch = bool(prefetch)          # extra knob: host batches are copied to the device one iteration ahead
         self.pipeline = bool(kwargs.pop("pipeline", True))   # extra knob: see train_iter
@@ -82,6 +85,20 @@ class Trainer:
             # the backends took the process's default scaler (ops_hip.HipOps): the trainer owns it for checkpoints and the log
             self.loss_scaler = hip_models[0].runtime()[0].amp
             self.loss_scaler.attach(*hip_models)
+        # generator weight averaging (rna_gan_amd.ema): built after the broadcast, so every rank's average starts from rank 0's
+        # generator; kept by one launch inside optimizer_generator.step().  The twin is NOT in model_names: the loop never puts
+        # it in train mode and the checkpoint keys of the models / optimizers are unchanged
+        self.ema = None
+        self.generator_ema = None
+        if ema_decay is not None:
+            from .ema import ParamEMA
+            opt = getattr(self, "optimizer_generator", None)
+            if not hasattr(self, "generator") or not isinstance(opt, optim.Adam):
+                raise ValueError("ema_decay needs a 'generator' model whose optimizer is rna_gan_amd.optim.Adam (or "
+                                 "torch.optim.Adam, which the Trainer replaces by it): the average is a launch of its step()")
+            self.ema = ParamEMA(self.generator, decay=ema_decay, warmup=ema_warmup)
+            opt.attach_ema(self.ema)
+            self.generator_ema = self.ema.module
         self.losses = {}
         for loss in losses_list:
             self.losses[type(loss).__name__] = loss
@@ -132,6 +149,9 @@ class Trainer:
             model.update({save_item: getattr(self, save_item).state_dict()})
         if self.loss_scaler is not None:
             model["loss_scaler"] = self.loss_scaler.state_dict()
+        if self.ema is not None:
+            model["generator_ema"] = self.ema.state_dict()
+            model["ema_information"] = {"decay": self.ema.decay, "warmup": self.ema.warmup}
         if save_items is not None:
             for it in ([save_items] if isinstance(save_items, str) else save_items):
                 model.update({it: getattr(self, it)})
@@ -165,6 +185,12 @@ class Trainer:
                 getattr(self, load_item).load_state_dict(checkpoint[load_item])
             if self.loss_scaler is not None and "loss_scaler" in checkpoint:
                 self.loss_scaler.load_state_dict(checkpoint["loss_scaler"])
+            if self.ema is not None:                       # (a "generator_ema" entry is ignored when averaging is off)
+                if "generator_ema" in checkpoint:
+                    self.ema.load_state_dict(checkpoint["generator_ema"])
+                else:
+                    self.ema.reset()
+                    print("load_model: the checkpoint holds no averaged generator: the average restarts from the loaded generator")
             if load_items is not None:
                 for it in ([load_items] if isinstance(load_items, str) else load_items):
                     obj = checkpoint[it]
@@ -310,6 +336,11 @@ class Trainer:
             img = gen(self.test_noise[0] if isinstance(self.test_noise, (list, tuple)) else self.test_noise)
         gen.train(was_training)
         save_image_grid(img, "{}/epoch{}_generator.png".format(self.recon, epoch + 1), nrow=self.nrow)
+        if self.ema is not None:                           # the averaged generator on the same noise
+            self.ema.sync_buffers()
+            with torch.no_grad():
+                img = self.generator_ema(self.test_noise[0] if isinstance(self.test_noise, (list, tuple)) else self.test_noise)
+            save_image_grid(img, "{}/epoch{}_generator_ema.png".format(self.recon, epoch + 1), nrow=self.nrow)
 
     def train(self, data_loader, **kwargs):
         for name in self.model_names:
