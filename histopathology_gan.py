@@ -77,6 +77,11 @@ EXTRA_FLAGS = [
     ("--g_ema", float, 0.0, "decay in [0, 1) of an exponential moving average of the generator's weights, kept on the device "
                             "inside the optimizer step and saved / sampled next to the generator (0 = off)"),
     ("--g_ema_warmup", int, 1, "1 = the average's decay is min(g_ema, (1 + t) / (10 + t)) at generator step t, 0 = constant"),
+    ("--fd_samples", int, 0, "evaluate a Frechet distance after every epoch (rna_gan_amd.metrics.FrechetDistance, logged in the "
+                             "checkpoint's metric_logs): the first N items of the dataset are held on the device as the real set "
+                             "and N images are generated from fixed noise (0 = off)"),
+    ("--fd_extractor", str, "discriminator", "features of --fd_samples: 'discriminator' (the labelled proxy: the critic's trunk, "
+                                             "comparable within one run only) or the path of a torchvision inception_v3 state dict"),
 ]
 
 
@@ -104,17 +109,63 @@ def shard_indices(n_items: int, rank: int, world: int, batch_size: int):
     return list(range(rank, n_items, world))[:per_rank]
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="GANs training on histology data (MI355X path)")
     for flag, typ, default, text in REFERENCE_FLAGS + EXTRA_FLAGS:
         ap.add_argument(flag, type=typ, default=default, help=text)
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic tiles / RNA rows")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if not 0.0 <= args.g_ema < 1.0:
         ap.error("--g_ema must be in [0, 1)")
     if args.g_ema_warmup not in (0, 1):
         ap.error("--g_ema_warmup must be 0 or 1")
+    if args.fd_samples < 0 or args.fd_samples == 1:
+        ap.error("--fd_samples must be 0 (off) or at least 2 (a covariance needs two samples)")
+    if args.fd_extractor != "discriminator" and not os.path.isfile(args.fd_extractor):
+        ap.error("--fd_extractor must be 'discriminator' or the path of an inception_v3 state dict (no such file: %s)"
+                 % args.fd_extractor)
     return args
+
+
+def build_fd_metric(args, ds, losses, device, holder):
+    """--fd_samples: the Frechet-distance metric over the first N items of ``ds`` (held on the device).  wganvae: the fake
+    noise is built ONCE from those items' RNA rows by generate_images' rule -- a uniform draw (here from the metric's private
+    generator, never the global one) plus the encoder's mean, standardised per column by rg_latent_prep over the metric's own
+    rows (no collective).  ``holder["trainer"]`` is filled in once the Trainer exists: the noise needs its generator."""
+    from rna_gan_amd import _abi
+    from rna_gan_amd.fid import inception_features_device
+    from rna_gan_amd.metrics import FrechetDistance
+    with_rna = args.loss_type == "wganvae"
+    items = [ds[i] for i in range(min(args.fd_samples, len(ds)))]
+    image_of = (lambda b: b["image"]) if with_rna else (lambda b: b[0])
+    items = [b for b in items if image_of(b) is not None]
+    if len(items) < 2:
+        raise SystemExit("--fd_samples: fewer than 2 readable tiles among the first %d items" % args.fd_samples)
+    real = torch.stack([image_of(b) for b in items]).to(device)
+    extractor = "discriminator" if args.fd_extractor == "discriminator" else inception_features_device(args.fd_extractor, device)
+    noise = None
+    if with_rna:
+        rna = torch.stack([b["rna_data"] for b in items])
+        private = torch.Generator().manual_seed(args.seed)
+        cache = {}
+
+        def noise(n):
+            if "z" not in cache:
+                trainer = holder["trainer"]
+                betavae = losses[0].betavae.to(device)
+                E = trainer.generator.encoding_dims
+                u = torch.empty(n, E).uniform_(-0.3, 0.3, generator=private).to(device).contiguous()
+                was_training = betavae.training
+                betavae.eval()                             # the frozen encoder: no dropout draw, no running-statistics update
+                with torch.no_grad():
+                    z = betavae.encode(rna.to(device))[0].detach().float().contiguous()
+                betavae.train(was_training)
+                out = torch.empty_like(u)
+                _abi.check(_abi.load().rg_latent_prep(u.data_ptr(), z.data_ptr(), out.data_ptr(), n, E,
+                                                      torch.cuda.current_stream(device).cuda_stream), "rg_latent_prep")
+                cache["z"] = out
+            return cache["z"]
+    return FrechetDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=min(256, len(items)))
 
 
 def main():
@@ -203,9 +254,12 @@ def main():
     device = torch.device("cuda", local)
     epochs = args.num_epochs if args.num_epochs is not None else 5
     print("Device: {}".format(device)); print("Epochs: {}".format(epochs))
-    trainer = P.Trainer(gan_network, losses, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
+    holder = {}
+    metrics = [build_fd_metric(args, ds, losses, device, holder)] if args.fd_samples > 0 and D_.rank() == 0 else None
+    trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,
                         ema_decay=args.g_ema if args.g_ema > 0.0 else None, ema_warmup=bool(args.g_ema_warmup))
+    holder["trainer"] = trainer
     if args.checkpoint is not None:
         trainer.load_model(load_path=args.checkpoint)
     for loss in losses:                                   # identical frozen encoders on every rank (rank 0's)

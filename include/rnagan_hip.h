@@ -44,6 +44,7 @@ extern "C" {
 
 #define RG_F32 0
 #define RG_BF16 1
+#define RG_U8 3    /* unsigned 8-bit image samples: a SOURCE type of rg_resize_bilinear01 only */
 #define RG_F16 2   /* IEEE fp16 storage: librnagan_hip_f16.so only (the same sources built with -DRG_HALF_F16; see "fp16 build" below) */
 
 #define RG_ALGO_AUTO 0
@@ -367,6 +368,35 @@ int rg_pool2d_nhwc(const float* x, int ldx, float* y, int ldy, int N, int H, int
 int rg_nchw_to_nhwc_affine(const float* x_nchw, float* y_nhwc, int N, int C, int H, int W, const float* scale, const float* shift,
                            void* stream);
 int rg_spatial_mean_nhwc(const float* x, float* y, int N, int HW, int C, void* stream);
+
+/* The two kernels a Frechet-distance evaluation needs around a feature extractor (rg_fidstat.hip; rna_gan_amd.fid
+ * preprocess_images_device / FeatureMoments, rna_gan_amd.metrics.FrechetDistance).  No 16-bit type is involved: both builds
+ * behave identically.
+ *
+ * rg_resize_bilinear01: bilinear resampling of an image batch to (Ho, Wo), half-pixel centres, no anti-aliasing (cv2.resize /
+ * F.interpolate(align_corners=False)); dst is fp32 NCHW [N][C][Ho][Wo] in [0, 1], what InceptionV3.features takes.  src is
+ * addressed as src[n*sn + c*sc + y*sh + x*sw] (ELEMENT strides: NCHW, NHWC and a slice of a larger batch are just strides).
+ *   tap     RG_U8: t = (float)v / 255.0f (a true division, as rg_u8_to_norm);  RG_F32: t = v * mul + add, two fp32 operations
+ *           ((1, 0) for images in [0, 1], (0.5, 0.5) for generator output in [-1, 1]; mul / add are ignored for RG_U8)
+ *   axis    in fp64: s = max(0, (d + 0.5) * (double)in / out - 0.5), i0 = min(floor(s), in - 1), i1 = min(i0 + 1, in - 1),
+ *           lambda = (float)(s - i0)
+ *   value   (1 - ly) * ((1 - lx) * t00 + lx * t01) + ly * ((1 - lx) * t10 + lx * t11), every operation a separately rounded
+ *           fp32 operation, then clamped into [0, 1] by comparisons (a NaN tap stays NaN).  in == out on both axes: the tap
+ *           bit for bit.
+ * Only the H x W taps of the N x C planes are read.  N == 0: RG_OK, nothing launched.  RG_EINVAL (nothing launched) for a
+ * NULL buffer, a non-positive size or a src_dtype other than RG_F32 / RG_U8. */
+int rg_resize_bilinear01(const void* src, int src_dtype, int64_t sn, int64_t sc, int64_t sh, int64_t sw, float mul, float add,
+                         float* dst_nchw, int N, int C, int H, int W, int Ho, int Wo, void* stream);
+/* rg_moments_update: first and second raw moments of n feature rows x[r][0..F) (row stride ldx >= F elements, any alignment),
+ * accumulated in fp64 into caller-zeroed s1[F] and s2[F][F] (row-major):
+ *   s1[j]    += sum_r x[r][j]
+ *   s2[i][j] += sum_r (double)x[r][i] * (double)x[r][j]
+ * The products are exact in fp64; the additions run in row order inside the ONE workgroup that owns a 64 x 64 tile of s2 (it
+ * reads the tile, adds its sum over the n rows, writes it back): no atomics, the same bits on every run, and s2[i][j] ==
+ * s2[j][i] bit for bit (each off-diagonal tile pair is computed once and written twice).  Only rows < n and columns < F of x
+ * are read.  Any F >= 1, any n >= 0 (n == 0: RG_OK, nothing launched); RG_EINVAL for F < 1, n < 0, ldx < F or a NULL buffer.
+ * (mu, sigma) = (s1 / n, (s2 - n mu mu^T) / (n - 1)) is finished on the host. */
+int rg_moments_update(const float* x, int ldx, int n, int F, double* s1, double* s2, void* stream);
 
 /* ---- split-K conv + train-mode BatchNorm without the intermediate passes (bf16 path) -------------------------------
  * The deep Conv2d / ConvTranspose2d layers at small batch run split-K (rg_conv_split(...) > 1): every launch leaves

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librnagan_hip.so")
 
 RG_F32, RG_BF16, RG_F16 = 0, 1, 2
+RG_U8 = 3            # a source type of rg_resize_bilinear01 only
 ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA = 0, 1, 2
 
 _p = C.c_void_p
@@ -18,6 +19,7 @@ _i = C.c_int
 _f = C.c_float
 _d = C.c_double
 _z = C.c_size_t
+_l = C.c_int64
 
 # name -> (restype, [argtypes])   -- must list every symbol declared in include/rnagan_hip.h
 PROTOTYPES = {
@@ -153,6 +155,8 @@ PROTOTYPES = {
     "rg_pool2d_nhwc": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rg_nchw_to_nhwc_affine": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "rg_spatial_mean_nhwc": (_i, [_p, _p, _i, _i, _i, _p]),
+    "rg_resize_bilinear01": (_i, [_p, _i, _l, _l, _l, _l, _f, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "rg_moments_update": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "rg_conv_split": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rg_conv_slab_dtype": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rg_conv_down_partial": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
@@ -191,7 +195,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES
-ABI_VERSION = 615
+ABI_VERSION = 616
 
 _libs = {}
 LIB_PATH_F16 = os.path.join(_HERE, "librnagan_hip_f16.so")

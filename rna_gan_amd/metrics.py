@@ -1,0 +1,164 @@
+"""Evaluation metrics of the torchgan ``Trainer`` interface (``Trainer(models, losses_list, metrics_list=[...])``).
+
+torchgan is third-party and its source is absent from the reference tree, so ``EvaluationMetric`` is torchgan's interface AS
+RECALLED (like the rest of the trainer): a metric has an ``arg_map`` that may rename the trainer
+attributes its ``metric_ops`` takes, ``set_arg_map``, ``preprocess``, ``calculate_score`` and ``metric_ops(...)``, which the
+trainer calls once per epoch with arguments resolved BY NAME and whose value it appends to ``metric_logs[<class name>]``.
+
+``FrechetDistance`` is the per-epoch quality signal on top of rna_gan_amd.fid's device path: generated images never leave
+the device, an evaluation moves F + F^2 doubles per image set to the host and computes one F x F matrix square root there.
+"""
+from __future__ import annotations
+
+import torch
+
+
+class EvaluationMetric:
+    """torchgan.metrics.EvaluationMetric (recalled): base class of everything in ``metrics_list``."""
+
+    def __init__(self):
+        self.arg_map = {}
+
+    def set_arg_map(self, value):
+        """Rename arguments of ``metric_ops``: {argument name: trainer attribute name}."""
+        self.arg_map.update(value)
+
+    def preprocess(self, x):
+        raise NotImplementedError
+
+    def calculate_score(self, x):
+        raise NotImplementedError
+
+    def metric_ops(self, generator, discriminator, **kwargs):
+        raise NotImplementedError
+
+
+class FrechetDistance(EvaluationMetric):
+    """Frechet distance between features of generated images and of a fixed real set, evaluated on the device.
+
+    real       (N, 3, S, S) tiles: uint8, or float normalised to [-1, 1] (what the discriminator takes); kept where it is
+               given (put it on the device once to keep evaluations free of uploads).
+    n_fake     number of generated images (default len(real)).
+    extractor  "discriminator": the labelled PROXY of fid.fid_proxy -- the discriminator trunk's features at native
+               resolution, no resize; comparable only within one run, and the real statistics are recomputed at every call
+               because the extractor moves with training.  A callable (fid.inception_features_device(weights)): images are
+               resized to 299 x 299 first and the real statistics are computed once and cached.
+    noise      None: (n_fake, E) standard normal values drawn ONCE from a private torch.Generator(seed) and reused at every
+               evaluation (drawn at construction when ``encoding_dims`` is given, else at the first evaluation from the
+               generator's ``encoding_dims`` -- the same values either way, the generator is private); a tensor: used as
+               given; a callable noise(n): called at every evaluation.
+    The metric never touches the global CPU or device random generators, puts both networks in eval mode under no_grad and
+    restores their modes: a training run with the metric is bit-identical to one without it.
+    Pickling (the trainer pickles its metrics into every checkpoint) keeps the settings only -- never the real set, the
+    noise or cached statistics; an unpickled metric has to be given its data again (``set_real``) before it can evaluate."""
+
+    def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None):
+        super().__init__()
+        if not (extractor == "discriminator" or callable(extractor)):
+            raise ValueError("extractor must be 'discriminator' or a callable device-side feature extractor")
+        self.extractor = extractor
+        self.seed = int(seed)
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self._rng = torch.Generator().manual_seed(self.seed)
+        self._real_stats = None
+        self.real = None
+        self.set_real(real)
+        self.n_fake = int(n_fake) if n_fake is not None else int(self.real.shape[0])
+        if self.n_fake < 2:
+            raise ValueError("n_fake must be >= 2")
+        if torch.is_tensor(noise) and noise.shape[0] != self.n_fake:
+            raise ValueError("noise has %d rows, n_fake is %d" % (noise.shape[0], self.n_fake))
+        self.noise = noise
+        if noise is None and encoding_dims is not None:
+            self.noise = torch.randn(self.n_fake, int(encoding_dims), generator=self._rng)
+
+    # ------------------------------------------------------------------ data
+    def set_real(self, real):
+        if not torch.is_tensor(real) or real.dim() != 4 or real.shape[1] != 3 or real.shape[0] < 2:
+            raise ValueError("real must be an (N >= 2, 3, S, S) tensor of tiles")
+        if real.dtype != torch.uint8 and not real.is_floating_point():
+            raise TypeError("real must be uint8 or float tiles")
+        self.real = real
+        self._real_stats = None
+
+    def __getstate__(self):
+        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
+                "extractor": self.extractor if isinstance(self.extractor, str) else "callable"}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.real = None
+        self.noise = None
+        self._real_stats = None
+        self._rng = torch.Generator().manual_seed(self.seed)
+
+    # ------------------------------------------------------------------ torchgan's hooks
+    def preprocess(self, x):
+        """A chunk of the real set on the device, in the form its consumer takes: [-1, 1] fp32 for the discriminator (uint8
+        tiles through rg_u8_to_norm, the training input transform); unchanged for the resize kernel, which reads uint8."""
+        if self.extractor != "discriminator" or x.dtype != torch.uint8:
+            return x if x.dtype == torch.uint8 else x.float()
+        from . import _abi
+        x = x.contiguous()
+        y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _abi.check(_abi.load().rg_u8_to_norm(x.data_ptr(), y.data_ptr(), x.numel(), 0.5, 0.5,
+                                                 torch.cuda.current_stream(x.device).cuda_stream), "rg_u8_to_norm")
+        return y
+
+    def calculate_score(self, fake_stats, real_stats=None):
+        (m1, s1), (m2, s2) = fake_stats[:2], real_stats[:2]
+        from .fid import frechet_distance
+        return frechet_distance(m1, s1, m2, s2)
+
+    # ------------------------------------------------------------------ evaluation
+    def _noise_for(self, generator, device):
+        if callable(self.noise):
+            z = self.noise(self.n_fake)
+        else:
+            if self.noise is None:
+                self.noise = torch.randn(self.n_fake, int(generator.encoding_dims), generator=self._rng)
+            z = self.noise
+        if z.shape[0] != self.n_fake:
+            raise ValueError("noise has %d rows, n_fake is %d" % (z.shape[0], self.n_fake))
+        return z.to(device).float()
+
+    def _fake_batches(self, generator, z):
+        from .gan_utils import synthesize
+        from .models import DCGANGenerator
+        for c in torch.split(z, self.batch_size):
+            if isinstance(generator, DCGANGenerator):
+                yield synthesize(generator, c, chunk=self.batch_size)
+            else:
+                yield generator(c.contiguous())
+
+    def _real_batches(self, device):
+        for i in range(0, self.real.shape[0], self.batch_size):
+            yield self.preprocess(self.real[i:i + self.batch_size].to(device))
+
+    @torch.no_grad()
+    def metric_ops(self, generator, discriminator, device):
+        if self.real is None:
+            raise RuntimeError("FrechetDistance: no real set (an unpickled metric keeps its settings only: call set_real)")
+        from . import fid as FID
+        modes = [(m, m.training) for m in (generator, discriminator)]
+        try:
+            for m, _ in modes:
+                m.eval()
+            if self.extractor == "discriminator":
+                extract, resize = FID.discriminator_features_device(discriminator), None
+            else:
+                extract, resize = self.extractor, 299
+            z = self._noise_for(generator, device)
+            fake = FID.device_statistics(self._fake_batches(generator, z), extract, resize=resize, value_range=(-1, 1))
+            real = self._real_stats
+            if real is None:
+                real = FID.device_statistics(self._real_batches(device), extract, resize=resize, value_range=(-1, 1))
+                if resize is not None:                       # a fixed extractor: the real statistics never change
+                    self._real_stats = real
+            return float(self.calculate_score(fake, real))
+        finally:
+            for m, was in modes:
+                m.train(was)

@@ -13,7 +13,9 @@ and absent from the reference tree; behaviour follows SURVEY.md Appendix A:
   * per epoch: checkpoint ``<checkpoints><k>.model`` (k cycling), console summary, sample grid
     ``<recon>/epoch<e+1>_generator.png`` from the generator in eval mode;
   * checkpoint dict keys: epoch, loss_information, loss_objects, metric_objects, loss_logs,
-    metric_logs, <model>, optimizer_<model>.
+    metric_logs, <model>, optimizer_<model>;
+  * per epoch, after the sample grid: every metric of ``metrics_list`` (rna_gan_amd.metrics) is evaluated by ``eval_ops``
+    and logged in ``metric_logs[<class name>]``.
 
 Extra (``ema_decay``): an exponential moving average of the generator's weights (rna_gan_amd.ema), exposed as
 ``generator_ema``, sampled to ``epoch<e+1>_generator_ema.png`` and saved under the extra keys generator_ema / ema_information.
@@ -116,7 +118,7 @@ class Trainer:
         self.loss_information = {"generator_losses": 0.0, "discriminator_losses": 0.0,
                                  "generator_iters": 0, "discriminator_iters": 0}
         self.loss_logs = {name: [] for name in self.losses}
-        self.metric_logs = {}
+        self.metric_logs = {name: [] for name in self.metrics}
         self.ncritic = ncritic
         self.start_epoch = 0
         self.last_retained_checkpoint = 0
@@ -181,6 +183,8 @@ class Trainer:
             for name in self.losses:                       # a log keyed by plugin names this trainer does not know stays
                 self.loss_logs.setdefault(name, [])        # (torchgan keeps it too); every live plugin needs its list
             self.metric_logs = checkpoint.get("metric_logs", self.metric_logs)
+            for name in self.metrics:                      # every live metric needs its list, as the losses above
+                self.metric_logs.setdefault(name, [])
             for load_item in self.model_names + self.optimizer_names:
                 getattr(self, load_item).load_state_dict(checkpoint[load_item])
             if self.loss_scaler is not None and "loss_scaler" in checkpoint:
@@ -342,10 +346,35 @@ class Trainer:
                 img = self.generator_ema(self.test_noise[0] if isinstance(self.test_noise, (list, tuple)) else self.test_noise)
             save_image_grid(img, "{}/epoch{}_generator_ema.png".format(self.recon, epoch + 1), nrow=self.nrow)
 
+    def _store_metric_maps(self):
+        self._metric_arg_maps = {name: self._get_argument_maps(metric.arg_map, metric.metric_ops)
+                                 for name, metric in self.metrics.items()}
+
+    def eval_ops(self, epoch):
+        """Once per epoch, after the sample grid: every metric's ``metric_ops`` with arguments resolved by name from the
+        trainer's attributes (``metric.arg_map`` may rename), its value appended to ``metric_logs[<name>]`` and printed.
+        Rank 0 only, like the checkpoint and the sample grid: the moments are not all-reduced, and the other ranks meet rank 0
+        at their next collective.  Every model's train / eval mode is put back afterwards.  (An epoch's checkpoint is written
+        before its evaluation, torchgan's order: the file of epoch e holds the values up to epoch e - 1.)"""
+        if not self.metrics or D_.rank() != 0:
+            return
+        if getattr(self, "_metric_arg_maps", None) is None or set(self._metric_arg_maps) != set(self.metrics):
+            self._store_metric_maps()
+        modes = [(getattr(self, name), getattr(self, name).training) for name in self.model_names]
+        try:
+            for name, metric in self.metrics.items():
+                value = metric.metric_ops(**self._get_arguments(self._metric_arg_maps[name]))
+                self.metric_logs.setdefault(name, []).append(value)
+                print("{} : {}".format(name, value))
+        finally:
+            for model, was_training in modes:
+                model.train(was_training)
+
     def train(self, data_loader, **kwargs):
         for name in self.model_names:
             getattr(self, name).train()
         self._store_loss_maps()
+        self._store_metric_maps()
         if self.test_noise is None:
             self.test_noise = self.generator.sampler(self.sample_size, self.device)
         for epoch in range(self.start_epoch, self.epochs):
@@ -382,6 +411,7 @@ class Trainer:
                     st = self.loss_scaler.state_dict()
                     print("loss scale : {:g}  skipped steps : {}".format(st["scale"], st["skipped_steps"]))
             self.sample_images(epoch)
+            self.eval_ops(epoch)
             for sch in self.schedulers:
                 sch.step()
         print("Training of the Model is Complete") if D_.rank() == 0 else None
