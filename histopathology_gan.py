@@ -82,6 +82,13 @@ EXTRA_FLAGS = [
                              "and N images are generated from fixed noise (0 = off)"),
     ("--fd_extractor", str, "discriminator", "features of --fd_samples: 'discriminator' (the labelled proxy: the critic's trunk, "
                                              "comparable within one run only) or the path of a torchvision inception_v3 state dict"),
+    ("--kid_samples", int, 0, "evaluate a kernel distance (KID: the unbiased MMD^2 under the cubic polynomial kernel, "
+                              "rna_gan_amd.metrics.KernelDistance) after every epoch on the first N items of the dataset and N "
+                              "generated images, features of --fd_extractor; with --fd_samples N the two metrics share the real "
+                              "set and the noise (0 = off)"),
+    ("--kid_subsets", int, 0, "--kid_samples: log the mean over K random row subsets instead of the full-set estimate (the "
+                              "published convention is 100; 0 = the full-set estimate)"),
+    ("--kid_subset_size", int, 1000, "--kid_subsets: rows per subset (clamped to the number of samples)"),
 ]
 
 
@@ -124,25 +131,37 @@ def parse_args(argv=None):
     if args.fd_extractor != "discriminator" and not os.path.isfile(args.fd_extractor):
         ap.error("--fd_extractor must be 'discriminator' or the path of an inception_v3 state dict (no such file: %s)"
                  % args.fd_extractor)
+    if args.kid_samples < 0 or args.kid_samples == 1:
+        ap.error("--kid_samples must be 0 (off) or at least 2 (the unbiased estimator divides by n - 1)")
+    if args.kid_subsets < 0:
+        ap.error("--kid_subsets must be >= 0")
+    if args.kid_subset_size < 2:
+        ap.error("--kid_subset_size must be at least 2")
     return args
 
 
-def build_fd_metric(args, ds, losses, device, holder):
-    """--fd_samples: the Frechet-distance metric over the first N items of ``ds`` (held on the device).  wganvae: the fake
-    noise is built ONCE from those items' RNA rows by generate_images' rule -- a uniform draw (here from the metric's private
-    generator, never the global one) plus the encoder's mean, standardised per column by rg_latent_prep over the metric's own
-    rows (no collective).  ``holder["trainer"]`` is filled in once the Trainer exists: the noise needs its generator."""
+def metric_inputs(args, n_samples, flag, ds, losses, device, holder):
+    """(real, extractor, noise, batch_size) of a per-epoch metric over the first ``n_samples`` items of ``ds`` (held on the
+    device).  wganvae: the fake noise is built ONCE from those items' RNA rows by generate_images' rule -- a uniform draw (here
+    from a private generator, never the global one) plus the encoder's mean, standardised per column by rg_latent_prep over
+    the metric's own rows (no collective).  ``holder["trainer"]`` is filled in once the Trainer exists: the noise needs its
+    generator.  ``holder`` also keeps what is built here, so two metrics over the same number of samples share one device copy of
+    the real set and one noise callable, and all metrics share one extractor."""
     from rna_gan_amd import _abi
     from rna_gan_amd.fid import inception_features_device
-    from rna_gan_amd.metrics import FrechetDistance
+    if "extractor" not in holder:
+        holder["extractor"] = "discriminator" if args.fd_extractor == "discriminator" else \
+            inception_features_device(args.fd_extractor, device)
+    shared = holder.setdefault("metric_inputs", {})
+    if n_samples in shared:
+        return shared[n_samples]
     with_rna = args.loss_type == "wganvae"
-    items = [ds[i] for i in range(min(args.fd_samples, len(ds)))]
+    items = [ds[i] for i in range(min(n_samples, len(ds)))]
     image_of = (lambda b: b["image"]) if with_rna else (lambda b: b[0])
     items = [b for b in items if image_of(b) is not None]
     if len(items) < 2:
-        raise SystemExit("--fd_samples: fewer than 2 readable tiles among the first %d items" % args.fd_samples)
+        raise SystemExit("%s: fewer than 2 readable tiles among the first %d items" % (flag, n_samples))
     real = torch.stack([image_of(b) for b in items]).to(device)
-    extractor = "discriminator" if args.fd_extractor == "discriminator" else inception_features_device(args.fd_extractor, device)
     noise = None
     if with_rna:
         rna = torch.stack([b["rna_data"] for b in items])
@@ -165,7 +184,24 @@ def build_fd_metric(args, ds, losses, device, holder):
                                                       torch.cuda.current_stream(device).cuda_stream), "rg_latent_prep")
                 cache["z"] = out
             return cache["z"]
-    return FrechetDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=min(256, len(items)))
+    shared[n_samples] = (real, holder["extractor"], noise, min(256, len(items)))
+    return shared[n_samples]
+
+
+def build_fd_metric(args, ds, losses, device, holder):
+    """--fd_samples: the Frechet-distance metric over the first N items of ``ds`` (metric_inputs)."""
+    from rna_gan_amd.metrics import FrechetDistance
+    real, extractor, noise, batch = metric_inputs(args, args.fd_samples, "--fd_samples", ds, losses, device, holder)
+    return FrechetDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch)
+
+
+def build_kid_metric(args, ds, losses, device, holder):
+    """--kid_samples: the kernel-distance metric over the first N items of ``ds`` (metric_inputs: with --fd_samples N the same
+    device copy of the real set and the same noise callable as the Frechet distance's)."""
+    from rna_gan_amd.metrics import KernelDistance
+    real, extractor, noise, batch = metric_inputs(args, args.kid_samples, "--kid_samples", ds, losses, device, holder)
+    return KernelDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch,
+                          num_subsets=args.kid_subsets, subset_size=args.kid_subset_size)
 
 
 def main():
@@ -255,7 +291,13 @@ def main():
     epochs = args.num_epochs if args.num_epochs is not None else 5
     print("Device: {}".format(device)); print("Epochs: {}".format(epochs))
     holder = {}
-    metrics = [build_fd_metric(args, ds, losses, device, holder)] if args.fd_samples > 0 and D_.rank() == 0 else None
+    metrics = []
+    if D_.rank() == 0:                                    # the per-epoch metrics are evaluated by rank 0 alone
+        if args.fd_samples > 0:
+            metrics.append(build_fd_metric(args, ds, losses, device, holder))
+        if args.kid_samples > 0:
+            metrics.append(build_kid_metric(args, ds, losses, device, holder))
+    metrics = metrics or None
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,
                         ema_decay=args.g_ema if args.g_ema > 0.0 else None, ema_warmup=bool(args.g_ema_warmup))

@@ -370,8 +370,8 @@ int rg_nchw_to_nhwc_affine(const float* x_nchw, float* y_nhwc, int N, int C, int
 int rg_spatial_mean_nhwc(const float* x, float* y, int N, int HW, int C, void* stream);
 
 /* The two kernels a Frechet-distance evaluation needs around a feature extractor (rg_fidstat.hip; rna_gan_amd.fid
- * preprocess_images_device / FeatureMoments, rna_gan_amd.metrics.FrechetDistance).  No 16-bit type is involved: both builds
- * behave identically.
+ * preprocess_images_device / FeatureMoments, rna_gan_amd.metrics.FrechetDistance) and the one kernel of the kernel distance
+ * (rna_gan_amd.kid, rna_gan_amd.metrics.KernelDistance).  No 16-bit type is involved: both builds behave identically.
  *
  * rg_resize_bilinear01: bilinear resampling of an image batch to (Ho, Wo), half-pixel centres, no anti-aliasing (cv2.resize /
  * F.interpolate(align_corners=False)); dst is fp32 NCHW [N][C][Ho][Wo] in [0, 1], what InceptionV3.features takes.  src is
@@ -397,6 +397,26 @@ int rg_resize_bilinear01(const void* src, int src_dtype, int64_t sn, int64_t sc,
  * are read.  Any F >= 1, any n >= 0 (n == 0: RG_OK, nothing launched); RG_EINVAL for F < 1, n < 0, ldx < F or a NULL buffer.
  * (mu, sigma) = (s1 / n, (s2 - n mu mu^T) / (n - 1)) is finished on the host. */
 int rg_moments_update(const float* x, int ldx, int n, int F, double* s1, double* s2, void* stream);
+/* rg_polykernel_tile_sums: the Gram sums of the kernel distance (rna_gan_amd.kid; KID, Binkowski et al. 2018): sums of the
+ * polynomial kernel k(x, y) = (gamma <x, y> + coef0)^degree over 64 x 64 tiles of row pairs, in fp64.
+ *   a: na rows of F fp32 features, row stride lda >= F elements, any alignment; b: nb rows, row stride ldb >= F, likewise.
+ *   Ta = ceil(na / 64), Tb = ceil(nb / 64); sums is a Ta x Tb row-major fp64 matrix, WRITTEN (not accumulated into):
+ *     sums[ti][tj] = sum of k(a_r, b_s) over the rows r < na of tile ti and s < nb of tile tj.
+ *   Rows past na / nb are masked out of the sum (k(0, y) = coef0^degree is not zero) and never read; columns past F are never
+ *   read.  Nothing outside Ta * Tb doubles of sums and Ta doubles of diag is written.
+ * Symmetric form, b == NULL: b = a, nb = na (ldb, nb are ignored).  Only tiles ti <= tj are computed; each value is stored to
+ *   [ti][tj] and [tj][ti] (the same bits), and diag[ti] = sum_r k(a_r, a_r) over tile ti's rows, taken from the diagonal tile's
+ *   own accumulators.  diag is required in this form; with b != NULL it must be NULL.  sums of the symmetric form equals sums of
+ *   the two-operand call on (a, a) bit for bit (the order of a tile's sum is invariant under transposing the tile).
+ * Arithmetic: every operand is converted to fp64; dot = sum_k a[k] * b[k] sequentially in ascending k (the products of fp32
+ *   values are exact in fp64: fma and mul + add give the same bits); t = gamma * dot + coef0 as two separately rounded
+ *   operations; v = t (degree 1), t * t (2), (t * t) * t (3).  A tile's up to 4096 values are added in one fixed order inside the
+ *   ONE workgroup that owns the tile pair: no atomics, no split of a tile, the same bits on every run.
+ * No host synchronisation, no allocation, safe under graph capture.  na == 0 or nb == 0: RG_OK, nothing written.  RG_EINVAL
+ * (nothing launched) for F < 1, na < 0, nb < 0, lda < F, ldb < F, degree outside 1..3, a NULL a or sums, a NULL diag in the
+ * symmetric form or a non-NULL diag with two operands; RG_EUNSUPPORTED for more than 2^31 - 1 tiles. */
+int rg_polykernel_tile_sums(const float* a, int lda, int na, const float* b, int ldb, int nb, int F, double gamma, double coef0,
+                            int degree, double* sums, double* diag, void* stream);
 
 /* ---- split-K conv + train-mode BatchNorm without the intermediate passes (bf16 path) -------------------------------
  * The deep Conv2d / ConvTranspose2d layers at small batch run split-K (rg_conv_split(...) > 1): every launch leaves

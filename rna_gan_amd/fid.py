@@ -308,9 +308,28 @@ def device_statistics(batches, extractor, resize=None, value_range=None):
     return mu, sigma, moments.n
 
 
-def fid_statistics_device(images, feature_extractor, batch_size=2, device=None):
-    """(mu, sigma, n) of calculate_fid(on_device=True) for ONE image set: host (N, H, W, 3) uint8 / float in [0, 1] images
-    (or a device tensor of that form) are uploaded once, then resized to 299, extracted and accumulated on the device."""
+def device_features(batches, extractor, resize=None, value_range=None):
+    """device_statistics' loop and checks, returning the features themselves: the (n, F) fp32 features of an iterable of device
+    image batches as ONE contiguous device tensor (what rna_gan_amd.kid's Gram sums read; nothing goes to the host)."""
+    feats = []
+    for batch in batches:
+        if resize is not None:
+            batch = preprocess_images_device(batch, resize, value_range)
+        f = extractor(batch)
+        if not (torch.is_tensor(f) and f.is_cuda):
+            raise TypeError("device_features needs an extractor that returns device tensors (discriminator_features_device, "
+                            "inception_features_device)")
+        if f.dim() != 2 or (feats and (f.shape[1] != feats[0].shape[1] or f.device != feats[0].device)):
+            raise ValueError("device_features: the extractor returned %s after %s" % (
+                tuple(f.shape), tuple(feats[0].shape) if feats else "nothing"))
+        feats.append(f.float())
+    if not feats:
+        raise ValueError("device_features: no batches")
+    return torch.cat(feats, dim=0).contiguous()
+
+
+def _device_image_set(images, device=None):
+    """host (N, H, W, 3) uint8 / float in [0, 1] images (or a device tensor of that form), uploaded once: uint8 or fp32"""
     if torch.is_tensor(images):
         x = images
     else:
@@ -324,5 +343,12 @@ def fid_statistics_device(images, feature_extractor, batch_size=2, device=None):
         x = x.to(device if device is not None else "cuda:0")
     if x.dtype != torch.uint8:
         x = x.float()
+    return x
+
+
+def fid_statistics_device(images, feature_extractor, batch_size=2, device=None):
+    """(mu, sigma, n) of calculate_fid(on_device=True) for ONE image set: host (N, H, W, 3) uint8 / float in [0, 1] images
+    (or a device tensor of that form) are uploaded once, then resized to 299, extracted and accumulated on the device."""
+    x = _device_image_set(images, device)
     return device_statistics((x[i:i + batch_size] for i in range(0, x.shape[0], batch_size)), feature_extractor, resize=299,
                              value_range=(0, 1))

@@ -7,6 +7,8 @@ trainer calls once per epoch with arguments resolved BY NAME and whose value it 
 
 ``FrechetDistance`` is the per-epoch quality signal on top of rna_gan_amd.fid's device path: generated images never leave
 the device, an evaluation moves F + F^2 doubles per image set to the host and computes one F x F matrix square root there.
+``KernelDistance`` is the unbiased counterpart on rna_gan_amd.kid: the same two feature sets, three fp64 Gram sums on the device
+(rg_polykernel_tile_sums), one double per 64 x 64 tile of row pairs to the host and no matrix function at all.
 """
 from __future__ import annotations
 
@@ -33,24 +35,10 @@ class EvaluationMetric:
         raise NotImplementedError
 
 
-class FrechetDistance(EvaluationMetric):
-    """Frechet distance between features of generated images and of a fixed real set, evaluated on the device.
-
-    real       (N, 3, S, S) tiles: uint8, or float normalised to [-1, 1] (what the discriminator takes); kept where it is
-               given (put it on the device once to keep evaluations free of uploads).
-    n_fake     number of generated images (default len(real)).
-    extractor  "discriminator": the labelled PROXY of fid.fid_proxy -- the discriminator trunk's features at native
-               resolution, no resize; comparable only within one run, and the real statistics are recomputed at every call
-               because the extractor moves with training.  A callable (fid.inception_features_device(weights)): images are
-               resized to 299 x 299 first and the real statistics are computed once and cached.
-    noise      None: (n_fake, E) standard normal values drawn ONCE from a private torch.Generator(seed) and reused at every
-               evaluation (drawn at construction when ``encoding_dims`` is given, else at the first evaluation from the
-               generator's ``encoding_dims`` -- the same values either way, the generator is private); a tensor: used as
-               given; a callable noise(n): called at every evaluation.
-    The metric never touches the global CPU or device random generators, puts both networks in eval mode under no_grad and
-    restores their modes: a training run with the metric is bit-identical to one without it.
-    Pickling (the trainer pickles its metrics into every checkpoint) keeps the settings only -- never the real set, the
-    noise or cached statistics; an unpickled metric has to be given its data again (``set_real``) before it can evaluate."""
+class _GeneratedAgainstReal(EvaluationMetric):
+    """What FrechetDistance and KernelDistance share: the real set, the private noise, the batches of both image sets and the
+    evaluation frame (eval mode under no_grad, modes restored, the real set's result cached for a fixed extractor).  A subclass
+    supplies ``metric_ops`` and what is collected from a set's batches."""
 
     def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None):
         super().__init__()
@@ -108,11 +96,6 @@ class FrechetDistance(EvaluationMetric):
                                                  torch.cuda.current_stream(x.device).cuda_stream), "rg_u8_to_norm")
         return y
 
-    def calculate_score(self, fake_stats, real_stats=None):
-        (m1, s1), (m2, s2) = fake_stats[:2], real_stats[:2]
-        from .fid import frechet_distance
-        return frechet_distance(m1, s1, m2, s2)
-
     # ------------------------------------------------------------------ evaluation
     def _noise_for(self, generator, device):
         if callable(self.noise):
@@ -139,9 +122,11 @@ class FrechetDistance(EvaluationMetric):
             yield self.preprocess(self.real[i:i + self.batch_size].to(device))
 
     @torch.no_grad()
-    def metric_ops(self, generator, discriminator, device):
+    def _collect_sets(self, generator, discriminator, device, collect):
+        """(fake, real): ``collect(batches, extract, resize)`` of the generated set and of the real set (the latter kept in
+        ``_real_stats`` for a fixed extractor), both networks in eval mode, their modes restored"""
         if self.real is None:
-            raise RuntimeError("FrechetDistance: no real set (an unpickled metric keeps its settings only: call set_real)")
+            raise RuntimeError("%s: no real set (an unpickled metric keeps its settings only: call set_real)" % type(self).__name__)
         from . import fid as FID
         modes = [(m, m.training) for m in (generator, discriminator)]
         try:
@@ -152,13 +137,97 @@ class FrechetDistance(EvaluationMetric):
             else:
                 extract, resize = self.extractor, 299
             z = self._noise_for(generator, device)
-            fake = FID.device_statistics(self._fake_batches(generator, z), extract, resize=resize, value_range=(-1, 1))
+            fake = collect(self._fake_batches(generator, z), extract, resize)
             real = self._real_stats
             if real is None:
-                real = FID.device_statistics(self._real_batches(device), extract, resize=resize, value_range=(-1, 1))
-                if resize is not None:                       # a fixed extractor: the real statistics never change
+                real = collect(self._real_batches(device), extract, resize)
+                if resize is not None:                       # a fixed extractor: the real set's result never changes
                     self._real_stats = real
-            return float(self.calculate_score(fake, real))
+            return fake, real
         finally:
             for m, was in modes:
                 m.train(was)
+
+
+class FrechetDistance(_GeneratedAgainstReal):
+    """Frechet distance between features of generated images and of a fixed real set, evaluated on the device.
+
+    real       (N, 3, S, S) tiles: uint8, or float normalised to [-1, 1] (what the discriminator takes); kept where it is
+               given (put it on the device once to keep evaluations free of uploads).
+    n_fake     number of generated images (default len(real)).
+    extractor  "discriminator": the labelled PROXY of fid.fid_proxy -- the discriminator trunk's features at native
+               resolution, no resize; comparable only within one run, and the real statistics are recomputed at every call
+               because the extractor moves with training.  A callable (fid.inception_features_device(weights)): images are
+               resized to 299 x 299 first and the real statistics are computed once and cached.
+    noise      None: (n_fake, E) standard normal values drawn ONCE from a private torch.Generator(seed) and reused at every
+               evaluation (drawn at construction when ``encoding_dims`` is given, else at the first evaluation from the
+               generator's ``encoding_dims`` -- the same values either way, the generator is private); a tensor: used as
+               given; a callable noise(n): called at every evaluation.
+    The metric never touches the global CPU or device random generators, puts both networks in eval mode under no_grad and
+    restores their modes: a training run with the metric is bit-identical to one without it.
+    Pickling (the trainer pickles its metrics into every checkpoint) keeps the settings only -- never the real set, the
+    noise or cached statistics; an unpickled metric has to be given its data again (``set_real``) before it can evaluate."""
+
+    def calculate_score(self, fake_stats, real_stats=None):
+        (m1, s1), (m2, s2) = fake_stats[:2], real_stats[:2]
+        from .fid import frechet_distance
+        return frechet_distance(m1, s1, m2, s2)
+
+    def metric_ops(self, generator, discriminator, device):
+        from . import fid as FID
+        fake, real = self._collect_sets(generator, discriminator, device, lambda batches, extract, resize: FID.device_statistics(
+            batches, extract, resize=resize, value_range=(-1, 1)))
+        return float(self.calculate_score(fake, real))
+
+
+class KernelDistance(_GeneratedAgainstReal):
+    """Kernel distance (KID, rna_gan_amd.kid) between features of generated images and of a fixed real set: the unbiased
+    estimate of MMD^2 under the polynomial kernel (gamma <a, b> + coef0)^degree, gamma=None meaning 1 / F.  The Gram sums run on
+    the device in fp64 (rg_polykernel_tile_sums); no covariance, no matrix square root.
+
+    ``real``, ``n_fake``, ``extractor``, ``noise``, ``seed``, ``batch_size``, ``encoding_dims``: as FrechetDistance, with the
+    same guarantees -- private noise, the global generators untouched, eval mode under no_grad with the modes restored, settings
+    only in a pickle, ``set_real``.  The real set's FEATURES are cached only for a fixed (callable) extractor.
+    num_subsets > 0: besides the full-set estimate, the estimate on ``num_subsets`` row subsets of ``subset_size`` rows (clamped
+    to the smaller set) drawn without replacement from a private torch.Generator(seed) -- the same subsets at every evaluation;
+    the published convention is 100 subsets of 1000.
+    ``metric_ops`` returns the full-set ``mmd2``, or ``subset_mean`` when subsets are used: lower is better, about 0 when the
+    two sets follow one distribution, and it can be slightly negative (the estimator is unbiased).  The whole dictionary of
+    kid.kernel_distance is kept in ``self.last``."""
+
+    def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None,
+                 num_subsets=0, subset_size=1000, degree=3, gamma=None, coef0=1.0):
+        super().__init__(real, n_fake, extractor, noise, seed, batch_size, encoding_dims)
+        self.num_subsets, self.subset_size, self.degree = int(num_subsets), int(subset_size), int(degree)
+        self.gamma, self.coef0 = (None if gamma is None else float(gamma)), float(coef0)
+        if self.num_subsets < 0:
+            raise ValueError("num_subsets must be >= 0")
+        if self.subset_size < 2:
+            raise ValueError("subset_size must be >= 2")
+        if self.degree not in (1, 2, 3):
+            raise ValueError("degree must be 1, 2 or 3")
+        if self.gamma is not None and not self.gamma > 0.0:
+            raise ValueError("gamma must be > 0 (or None for 1 / F)")
+        self.last = None
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state.update(num_subsets=self.num_subsets, subset_size=self.subset_size, degree=self.degree, gamma=self.gamma,
+                     coef0=self.coef0)
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.last = None
+
+    def calculate_score(self, fake_feats, real_feats=None):
+        from .kid import kernel_distance
+        return kernel_distance(fake_feats, real_feats, num_subsets=self.num_subsets, subset_size=self.subset_size, seed=self.seed,
+                               gamma=self.gamma, coef0=self.coef0, degree=self.degree)
+
+    def metric_ops(self, generator, discriminator, device):
+        from . import fid as FID
+        fake, real = self._collect_sets(generator, discriminator, device, lambda batches, extract, resize: FID.device_features(
+            batches, extract, resize=resize, value_range=(-1, 1)))
+        self.last = self.calculate_score(fake, real)
+        return float(self.last["subset_mean"] if self.num_subsets > 0 else self.last["mmd2"])
