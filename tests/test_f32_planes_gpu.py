@@ -51,10 +51,9 @@ def test_conv_down_up_on_planes(products, tol, N, H, I, O, monkeypatch):
     ref = F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), stride=2, padding=1).permute(0, 2, 3, 1)
     scale = float(ref.abs().max())
     assert y.dtype == torch.float32 and float((y.double() - ref).abs().max()) <= tol * scale
-    if st is not None:      # BatchNorm column sums from the epilogue (unsplit launches)
-        s = st.double().sum(0)
-        assert float((s[0] - ref.reshape(-1, O).sum(0)).abs().max()) <= 1e-4 * float(ref.reshape(-1, O).abs().sum(0).max())
-        assert float((s[1] - (ref * ref).reshape(-1, O).sum(0)).abs().max()) <= 1e-4 * float((ref * ref).reshape(-1, O).sum(0).max())
+    # (all three shapes plan split-K, which writes no BatchNorm column sums; the epilogue's sums are held to 1e-4 at an unsplit
+    # shape by test_f32_planes_ops_gpu.py::test_hipops_gaussian_against_fp64, and exactly by its statistics test)
+    assert st is None and ops.lib.rg_f32p_conv_stats_rows(0, N, H // 2, H // 2, O, I, products) == 0
     gy = torch.randn(N, H // 2, H // 2, O, generator=g).cuda()
     if ops.lib.rg_f32p_conv_supported(1, N, H // 2, H // 2, O, I, products):
         gx = ops.conv_up(gy, cw)
