@@ -89,6 +89,13 @@ EXTRA_FLAGS = [
     ("--kid_subsets", int, 0, "--kid_samples: log the mean over K random row subsets instead of the full-set estimate (the "
                               "published convention is 100; 0 = the full-set estimate)"),
     ("--kid_subset_size", int, 1000, "--kid_subsets: rows per subset (clamped to the number of samples)"),
+    ("--pr_samples", int, 0, "evaluate precision, recall, density and coverage (k-nearest-neighbour manifold estimates, "
+                             "rna_gan_amd.metrics.PrecisionRecall) after every epoch on the first N items of the dataset and N "
+                             "generated images, features of --fd_extractor; with --fd_samples N and / or --kid_samples N the "
+                             "metrics share the real set and the noise (0 = off, otherwise at least --pr_k + 1)"),
+    ("--pr_k", int, 5, "--pr_samples: the neighbourhood size k (1..16)"),
+    ("--pr_report", str, "recall", "--pr_samples: which of precision, recall, density, coverage is logged in metric_logs (all "
+                                   "four are kept per epoch in the checkpointed metric's history)"),
 ]
 
 
@@ -137,6 +144,12 @@ def parse_args(argv=None):
         ap.error("--kid_subsets must be >= 0")
     if args.kid_subset_size < 2:
         ap.error("--kid_subset_size must be at least 2")
+    if not 1 <= args.pr_k <= 16:
+        ap.error("--pr_k must be in 1..16")
+    if args.pr_samples < 0 or 0 < args.pr_samples <= args.pr_k:
+        ap.error("--pr_samples must be 0 (off) or at least --pr_k + 1 (a k-th neighbour needs k other samples)")
+    if args.pr_report not in ("precision", "recall", "density", "coverage"):
+        ap.error("--pr_report must be precision, recall, density or coverage")
     return args
 
 
@@ -202,6 +215,18 @@ def build_kid_metric(args, ds, losses, device, holder):
     real, extractor, noise, batch = metric_inputs(args, args.kid_samples, "--kid_samples", ds, losses, device, holder)
     return KernelDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch,
                           num_subsets=args.kid_subsets, subset_size=args.kid_subset_size)
+
+
+def build_pr_metric(args, ds, losses, device, holder):
+    """--pr_samples: precision / recall / density / coverage over the first N items of ``ds`` (metric_inputs: with --fd_samples N
+    or --kid_samples N the same device copy of the real set, the same noise callable and the same extractor)."""
+    from rna_gan_amd.metrics import PrecisionRecall
+    real, extractor, noise, batch = metric_inputs(args, args.pr_samples, "--pr_samples", ds, losses, device, holder)
+    if real.shape[0] < args.pr_k + 1:
+        raise SystemExit("--pr_samples: %d readable tiles among the first %d items, --pr_k %d needs %d"
+                         % (real.shape[0], args.pr_samples, args.pr_k, args.pr_k + 1))
+    return PrecisionRecall(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch, nearest_k=args.pr_k,
+                           report=args.pr_report)
 
 
 def main():
@@ -297,6 +322,8 @@ def main():
             metrics.append(build_fd_metric(args, ds, losses, device, holder))
         if args.kid_samples > 0:
             metrics.append(build_kid_metric(args, ds, losses, device, holder))
+        if args.pr_samples > 0:
+            metrics.append(build_pr_metric(args, ds, losses, device, holder))
     metrics = metrics or None
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,

@@ -418,6 +418,37 @@ int rg_moments_update(const float* x, int ldx, int n, int F, double* s1, double*
 int rg_polykernel_tile_sums(const float* a, int lda, int na, const float* b, int ldb, int nb, int F, double gamma, double coef0,
                             int degree, double* sums, double* diag, void* stream);
 
+/* The two primitives of the precision / recall / density / coverage metrics (rg_knn.hip; rna_gan_amd.prdc,
+ * rna_gan_amd.metrics.PrecisionRecall; Kynkaanniemi et al. 2019, Naeem et al. 2020): k-th nearest-neighbour radii of a set and
+ * membership of the rows of one set in the balls of another.  All-pairs SQUARED distances in fp64 over 64 x 64 tiles of row
+ * pairs; the n x n matrix is never in memory.  No 16-bit type is involved: both builds behave identically.
+ *   Rows: fp32, F features, row stride lda / ldb >= F elements, any alignment.  Rows past the end and columns past F are never
+ *   read; nothing outside the outputs and the first rg_pairdist_ws_bytes(...) bytes of ws is written.
+ * Arithmetic: every operand is converted to fp64; diff = (double)a_f - (double)b_f is one rounded subtraction;
+ *   d2(a, b) = sum_f diff^2 is accumulated sequentially in ascending f by fma(diff, diff, acc).  Consequences, relied upon:
+ *   d2 >= 0; d2(a, a) = 0; d2(a, b) and d2(b, a) are the same bits; the value does not depend on tiling.  (The Gram form
+ *   |a|^2 + |b|^2 - 2 <a, b> is deliberately not used: it cancels, can go negative and breaks the exact symmetry.)  A NaN d2
+ *   never hits and counts as +inf in the selection and in the minimum.  Everything downstream of d2 (k-th smallest, count,
+ *   minimum) is independent of order: no atomics, the same bits on every run.
+ * rg_knn_radii2: r2[i] = the k-th smallest element of the multiset { d2(a_i, a_j) : j != i }, 1 <= k <= 16, n >= k + 1.  Row i
+ *   is excluded BY INDEX, not by value: a duplicate row at distance 0 counts, so a radius can be 0.  Each pair of tiles is
+ *   computed once (upper triangle) and serves both of its row sets.
+ * rg_radius_hits: for every row r < na of a,
+ *     count[r] = #{ s < nb : d2(a_r, b_s) <= rb2[s] }      (<= on squared distances, no square root anywhere)
+ *     mind2[r] = min_s d2(a_r, b_s)
+ *   rb2 == NULL: only mind2 is wanted, and count must be NULL too (count without rb2, or rb2 without count: RG_EINVAL).
+ * Workspace: rg_pairdist_ws_bytes(na, nb, k) bytes, 8-byte aligned, contents irrelevant before and after: per-tile partials
+ *   that a second small kernel (one thread per row) merges.  rg_knn_radii2 needs rg_pairdist_ws_bytes(n, n, k);
+ *   rg_radius_hits needs rg_pairdist_ws_bytes(na, nb, 0).  (0 for arguments out of range.)
+ * No host synchronisation, no allocation, safe under graph capture.  rg_radius_hits with na == 0 or nb == 0: RG_OK, nothing
+ * written.  Nothing is launched on an error: RG_EINVAL for F < 1, a negative row count, lda / ldb < F, k outside 1..16,
+ * n < k + 1, a NULL required buffer (a, b, ws, r2, mind2) or a misaligned ws; RG_EUNSUPPORTED for more than 2^31 - 1 tiles;
+ * RG_EWORKSPACE for ws_bytes below the size above. */
+size_t rg_pairdist_ws_bytes(int na, int nb, int k);
+int rg_knn_radii2(const float* a, int lda, int n, int F, int k, void* ws, size_t ws_bytes, double* r2, void* stream);
+int rg_radius_hits(const float* a, int lda, int na, const float* b, int ldb, int nb, int F, const double* rb2, void* ws,
+                   size_t ws_bytes, int32_t* count, double* mind2, void* stream);
+
 /* ---- split-K conv + train-mode BatchNorm without the intermediate passes (bf16 path) -------------------------------
  * The deep Conv2d / ConvTranspose2d layers at small batch run split-K (rg_conv_split(...) > 1): every launch leaves
  * nsplit fp32 slabs [nsplit][rows][C] in the workspace.  rg_conv_down_partial / rg_conv_up_partial run ONLY that launch

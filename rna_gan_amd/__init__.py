@@ -8,8 +8,8 @@ from .losses import (WassersteinDiscriminatorLoss, WassersteinDiscriminatorLossV
 from .trainer import Trainer  # noqa: F401
 from .optim import Adam  # noqa: F401
 from .ema import ParamEMA  # noqa: F401
-from .metrics import EvaluationMetric, FrechetDistance, KernelDistance  # noqa: F401
+from .metrics import EvaluationMetric, FrechetDistance, KernelDistance, PrecisionRecall  # noqa: F401
 
-__all__ = ["DCGANGenerator", "DCGANUpGenerator", "DCGANDiscriminator", "Generator", "Discriminator", "betaVAE", "Trainer", "Adam", "ParamEMA", "EvaluationMetric", "FrechetDistance", "KernelDistance",
+__all__ = ["DCGANGenerator", "DCGANUpGenerator", "DCGANDiscriminator", "Generator", "Discriminator", "betaVAE", "Trainer", "Adam", "ParamEMA", "EvaluationMetric", "FrechetDistance", "KernelDistance", "PrecisionRecall",
            "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss", "WassersteinGradientPenalty",
            "WassersteinGeneratorLossVAE", "WassersteinDiscriminatorLossVAE", "WassersteinGradientPenaltyVAE"]

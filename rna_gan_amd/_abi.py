@@ -158,6 +158,9 @@ PROTOTYPES = {
     "rg_resize_bilinear01": (_i, [_p, _i, _l, _l, _l, _l, _f, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rg_moments_update": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "rg_polykernel_tile_sums": (_i, [_p, _i, _i, _p, _i, _i, _i, _d, _d, _i, _p, _p, _p]),
+    "rg_pairdist_ws_bytes": (_z, [_i, _i, _i]),
+    "rg_knn_radii2": (_i, [_p, _i, _i, _i, _i, _p, _z, _p, _p]),
+    "rg_radius_hits": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _z, _p, _p, _p]),
     "rg_conv_split": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rg_conv_slab_dtype": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rg_conv_down_partial": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
@@ -196,7 +199,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES
-ABI_VERSION = 617
+ABI_VERSION = 618
 
 _libs = {}
 LIB_PATH_F16 = os.path.join(_HERE, "librnagan_hip_f16.so")

@@ -9,6 +9,8 @@ trainer calls once per epoch with arguments resolved BY NAME and whose value it 
 the device, an evaluation moves F + F^2 doubles per image set to the host and computes one F x F matrix square root there.
 ``KernelDistance`` is the unbiased counterpart on rna_gan_amd.kid: the same two feature sets, three fp64 Gram sums on the device
 (rg_polykernel_tile_sums), one double per 64 x 64 tile of row pairs to the host and no matrix function at all.
+``PrecisionRecall`` separates what those two distances mix -- fidelity (precision, density) and diversity (recall, coverage) --
+by k-nearest-neighbour balls in the same feature space (rna_gan_amd.prdc: rg_knn_radii2, rg_radius_hits); four numbers come back.
 """
 from __future__ import annotations
 
@@ -36,7 +38,7 @@ class EvaluationMetric:
 
 
 class _GeneratedAgainstReal(EvaluationMetric):
-    """What FrechetDistance and KernelDistance share: the real set, the private noise, the batches of both image sets and the
+    """What FrechetDistance, KernelDistance and PrecisionRecall share: the real set, the private noise, the batches of both image sets and the
     evaluation frame (eval mode under no_grad, modes restored, the real set's result cached for a fixed extractor).  A subclass
     supplies ``metric_ops`` and what is collected from a set's batches."""
 
@@ -231,3 +233,71 @@ class KernelDistance(_GeneratedAgainstReal):
             batches, extract, resize=resize, value_range=(-1, 1)))
         self.last = self.calculate_score(fake, real)
         return float(self.last["subset_mean"] if self.num_subsets > 0 else self.last["mmd2"])
+
+
+class PrecisionRecall(_GeneratedAgainstReal):
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) between features of
+    generated images and of a fixed real set (rna_gan_amd.prdc): both manifolds are estimated by the k-nearest-neighbour balls of
+    their rows.  precision / density fall when generated tiles leave the real manifold (low fidelity); recall / coverage fall
+    when the generator produces only a few of the real patterns (mode collapse) -- which a single distance cannot tell apart.
+    Radii and memberships run on the device in fp64 (rg_knn_radii2, rg_radius_hits), comparisons are ``<=`` on squared distances.
+
+    ``real``, ``n_fake``, ``extractor``, ``noise``, ``seed``, ``batch_size``, ``encoding_dims``: as FrechetDistance, with the
+    same guarantees -- private noise, the global generators untouched, eval mode under no_grad with the modes restored, ``set_real``.
+    nearest_k  the neighbourhood size k, 1..16; both sets need at least k + 1 rows.
+    report     which of "precision", "recall", "density", "coverage" ``metric_ops`` returns (what the trainer logs: one float
+               per epoch).  The whole dictionary of the evaluation is kept in ``self.last`` and appended to ``self.history``.
+    Pickling keeps the settings AND ``history`` (four floats per epoch, so a checkpoint holds all four values of every epoch),
+    never the real set, the noise or cached features.  For a fixed (callable) extractor the real set's features and its radii
+    are computed once and cached."""
+
+    REPORTS = ("precision", "recall", "density", "coverage")
+
+    def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None,
+                 nearest_k=5, report="recall"):
+        self.nearest_k = int(nearest_k)
+        if not 1 <= self.nearest_k <= 16:
+            raise ValueError("nearest_k must be in 1..16")
+        if report not in self.REPORTS:
+            raise ValueError("report must be one of %s" % ", ".join(self.REPORTS))
+        self.report = report
+        self.last, self.history = None, []
+        self._real_radii = None
+        super().__init__(real, n_fake, extractor, noise, seed, batch_size, encoding_dims)
+        if self.n_fake < self.nearest_k + 1:
+            raise ValueError("n_fake is %d: nearest_k = %d needs at least %d generated images" % (self.n_fake, self.nearest_k, self.nearest_k + 1))
+
+    def set_real(self, real):
+        super().set_real(real)
+        if self.real.shape[0] < self.nearest_k + 1:
+            raise ValueError("real has %d tiles: nearest_k = %d needs at least %d" % (self.real.shape[0], self.nearest_k, self.nearest_k + 1))
+        self._real_radii = None
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state.update(nearest_k=self.nearest_k, report=self.report, history=[dict(h) for h in self.history])
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.last = None
+        self._real_radii = None
+        self.history = [dict(h) for h in state.get("history", [])]
+
+    def calculate_score(self, fake_feats, real_feats=None, real_radii2=None):
+        from .prdc import prdc
+        return prdc(real_feats, fake_feats, k=self.nearest_k, real_radii2=real_radii2)
+
+    def metric_ops(self, generator, discriminator, device):
+        from . import fid as FID
+        from .prdc import knn_radii2
+        fake, real = self._collect_sets(generator, discriminator, device, lambda batches, extract, resize: FID.device_features(
+            batches, extract, resize=resize, value_range=(-1, 1)))
+        radii = self._real_radii
+        if radii is None:
+            radii = knn_radii2(real, self.nearest_k)
+            if self._real_stats is not None:                 # a fixed extractor: the real features are cached, so are their radii
+                self._real_radii = radii
+        self.last = self.calculate_score(fake, real, radii)
+        self.history.append(dict(self.last))
+        return float(self.last[self.report])
