@@ -10,7 +10,8 @@ The reference script itself cannot start (absent modules wsi_model/biggan/sagan,
 through rna_gan_amd.data (the reference's tile-record format, per-slide sampling and RNA log / StandardScaler
 preparation; slide databases as LMDB files when the ``lmdb`` package is installed, or as directory stores);
 ``--synthetic`` trains on synthetic tiles / RNA rows of the right shapes (what bench.py measures).  Extra flags: --batch_size (reference hard-codes 8),
---precision, --betavae_checkpoint, --steps_per_epoch.
+--precision, --betavae_checkpoint, --steps_per_epoch; --device_transform 1 hands the uint8 tiles to the device and normalises
+them there, --augment d4 applies one of the eight symmetries of the square per real sample (rna_gan_amd.augment).
 """
 import argparse
 import datetime
@@ -31,10 +32,11 @@ from rna_gan_amd import dist as D_
 
 class SyntheticTiles(Dataset):
     """uint8 uniform tiles -> float -> (x-0.5)/0.5 (src/histopathology_gan.py:106-109) and N(0,1) RNA rows
-    (StandardScaler output, :148-151) with 16 distinct rows (tiles of a slide share RNA)."""
+    (StandardScaler output, :148-151) with 16 distinct rows (tiles of a slide share RNA).  ``as_u8``: the same draws as the
+    uint8 tiles themselves (--device_transform 1: normalised on the device)."""
 
-    def __init__(self, n, img_size, rna_features, with_rna, seed):
-        self.n, self.s, self.f, self.with_rna = n, img_size, rna_features, with_rna
+    def __init__(self, n, img_size, rna_features, with_rna, seed, as_u8=False):
+        self.n, self.s, self.f, self.with_rna, self.as_u8 = n, img_size, rna_features, with_rna, as_u8
         rng = np.random.default_rng(seed)
         self.rows = torch.from_numpy(rng.normal(size=(16, rna_features)).astype(np.float32))
         self.seed = seed
@@ -44,8 +46,9 @@ class SyntheticTiles(Dataset):
 
     def __getitem__(self, i):
         rng = np.random.default_rng([self.seed, i])
-        img = torch.from_numpy(rng.integers(0, 256, size=(3, self.s, self.s), dtype=np.uint8)).float() / 255.0
-        img = (img - 0.5) / 0.5
+        img = torch.from_numpy(rng.integers(0, 256, size=(3, self.s, self.s), dtype=np.uint8))
+        if not self.as_u8:
+            img = (img.float() / 255.0 - 0.5) / 0.5
         if self.with_rna:
             return {"image": img, "rna_data": self.rows[i % 16], "labels": torch.tensor(0.0)}
         return img, torch.tensor(0.0)
@@ -96,6 +99,12 @@ EXTRA_FLAGS = [
     ("--pr_k", int, 5, "--pr_samples: the neighbourhood size k (1..16)"),
     ("--pr_report", str, "recall", "--pr_samples: which of precision, recall, density, coverage is logged in metric_logs (all "
                                    "four are kept per epoch in the checkpointed metric's history)"),
+    ("--device_transform", int, 0, "1 = the loader hands over uint8 tiles (a quarter of the host-to-device bytes) and one launch "
+                                   "normalises them on the device, bit-identical to the host transform "
+                                   "(rna_gan_amd.augment.InputTransform); 0 = the reference's host transform"),
+    ("--augment", str, "none", "none, or d4: every real sample of a training batch is mapped by one of the eight symmetries of "
+                               "the square (four rotations, each with or without a flip) drawn per sample from --seed, the rank "
+                               "and the batch counter, in the same launch; works on the float batch under --device_transform 0"),
 ]
 
 
@@ -150,6 +159,10 @@ def parse_args(argv=None):
         ap.error("--pr_samples must be 0 (off) or at least --pr_k + 1 (a k-th neighbour needs k other samples)")
     if args.pr_report not in ("precision", "recall", "density", "coverage"):
         ap.error("--pr_report must be precision, recall, density or coverage")
+    if args.device_transform not in (0, 1):
+        ap.error("--device_transform must be 0 or 1")
+    if args.augment not in ("none", "d4"):
+        ap.error("--augment must be none or d4")
     return args
 
 
@@ -174,7 +187,10 @@ def metric_inputs(args, n_samples, flag, ds, losses, device, holder):
     items = [b for b in items if image_of(b) is not None]
     if len(items) < 2:
         raise SystemExit("%s: fewer than 2 readable tiles among the first %d items" % (flag, n_samples))
-    real = torch.stack([image_of(b) for b in items]).to(device)
+    real = torch.stack([image_of(b) for b in items])
+    if real.dtype == torch.uint8:                          # --device_transform 1: unaugmented, scaled as the training batches
+        real = holder["input_transform"].normalize(real, device)
+    real = real.to(device)
     noise = None
     if with_rna:
         rna = torch.stack([b["rna_data"] for b in items])
@@ -252,9 +268,13 @@ def main():
     img_size = config["img_size"]
     rna_features = config.get("rna_features", 19198)
     with_rna = args.loss_type == "wganvae"
+    input_transform = None
+    if args.device_transform or args.augment != "none":
+        from rna_gan_amd.augment import InputTransform
+        input_transform = InputTransform(0.5, 0.5, augment=args.augment, seed=args.seed, rank=D_.rank())
     if args.synthetic:
         ds = SyntheticTiles(args.steps_per_epoch * args.batch_size, img_size, rna_features, with_rna,
-                            args.seed + 1000 * D_.rank())
+                            args.seed + 1000 * D_.rank(), as_u8=bool(args.device_transform))
         loader = DataLoader(ds, batch_size=args.batch_size, num_workers=0, pin_memory=True, drop_last=True)
     else:
         # the reference's data path (src/histopathology_gan.py:111-168): slide tables -> [log + StandardScaler on the
@@ -267,7 +287,7 @@ def main():
         random.seed(args.seed)
         patch_data_path = config["patch_data_path"]
         train_df = PD.load_slide_tables(config["path_csv"], patch_data_path)
-        tf = PD.ToFloatNormalize(0.5, 0.5)
+        tf = None if args.device_transform else PD.ToFloatNormalize(0.5, 0.5)   # None: uint8 tiles, normalised on the device
         if with_rna:
             train_df, _, _ = PD.log_standardize_rna(train_df)
             ds = PD.PatchRNADataset(patch_data_path, train_df, img_size, max_patches_total=args.num_patches, transforms=tf)
@@ -315,7 +335,7 @@ def main():
     device = torch.device("cuda", local)
     epochs = args.num_epochs if args.num_epochs is not None else 5
     print("Device: {}".format(device)); print("Epochs: {}".format(epochs))
-    holder = {}
+    holder = {"input_transform": input_transform}
     metrics = []
     if D_.rank() == 0:                                    # the per-epoch metrics are evaluated by rank 0 alone
         if args.fd_samples > 0:
@@ -327,7 +347,8 @@ def main():
     metrics = metrics or None
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,
-                        ema_decay=args.g_ema if args.g_ema > 0.0 else None, ema_warmup=bool(args.g_ema_warmup))
+                        ema_decay=args.g_ema if args.g_ema > 0.0 else None, ema_warmup=bool(args.g_ema_warmup),
+                        input_transform=input_transform)
     holder["trainer"] = trainer
     if args.checkpoint is not None:
         trainer.load_model(load_path=args.checkpoint)

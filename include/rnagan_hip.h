@@ -44,7 +44,7 @@ extern "C" {
 
 #define RG_F32 0
 #define RG_BF16 1
-#define RG_U8 3    /* unsigned 8-bit image samples: a SOURCE type of rg_resize_bilinear01 only */
+#define RG_U8 3    /* unsigned 8-bit image samples: a SOURCE type only (rg_resize_bilinear01, rg_tile_transform) */
 #define RG_F16 2   /* IEEE fp16 storage: librnagan_hip_f16.so only (the same sources built with -DRG_HALF_F16; see "fp16 build" below) */
 
 #define RG_ALGO_AUTO 0
@@ -809,6 +809,26 @@ int rg_selftest_fp8(int* detail, void* stream);
  * (uint8 CHW tiles stay CHW).  The same three fp32 operations as the host transform: bit-identical to it.  Lets the
  * loader hand over uint8 tiles (a quarter of the PCIe bytes) and normalise on the device. */
 int rg_u8_to_norm(const void* src_u8, float* dst, size_t n, float mean, float stdv, void* stream);
+
+/* The device-side input transform of the Trainer (rna_gan_amd.augment.InputTransform; rna_gan_amd/csrc/rg_augment.hip): normalise
+ * a tile batch and apply one of the eight symmetries of the square (the dihedral group D4) per sample, in one launch.
+ *   src   [N][C][S][S], RG_U8 or RG_F32;  dst [N][C][S][S] fp32 (the NCHW image the step's image-side kernels take)
+ *   value RG_U8: v = ((float)b / 255.0f - mean) / stdv, the three fp32 operations of rg_u8_to_norm in the same order (a true
+ *         division, no reciprocal, no contraction): bit-identical to it and to the host transform.  RG_F32: v is copied
+ *         unchanged and mean / stdv are ignored (a loader that already normalised).
+ *   codes device array of N ints, or NULL = code 0 for every sample.  Sample n uses c = codes[n] & 7 (any int is memory-safe);
+ *         all C planes of a sample get the same code.  c = r + 4 f: flip left-right if f, then rotate counter-clockwise by r
+ *         quarter turns (np.rot90(x[..., ::-1] if f else x, r, axes=(-2, -1))).  With T = S - 1, dst[i][j] = src[..]:
+ *           0: [i][j]      1: [j][T-i]    2: [T-i][T-j]    3: [T-j][i]
+ *           4: [i][T-j]    5: [j][i]      6: [T-i][j]      7: [T-j][T-i]
+ * Any S >= 1; no workspace; no alignment beyond the element type's (S % 4 == 0 with a 4-byte-aligned uint8 / 16-byte-aligned
+ * fp32 source and a 16-byte-aligned dst takes the vector path, same bits).  Nothing outside the two tensors is read or written;
+ * src and dst must not overlap.  No host synchronisation, no allocation, safe under graph capture.  N == 0: RG_OK, nothing
+ * launched.  RG_EINVAL (nothing launched) for a NULL src or dst, N < 0, C <= 0, S <= 0, a src_dtype other than RG_U8 / RG_F32,
+ * or stdv == 0 with RG_U8; RG_EUNSUPPORTED for more than 2^31 - 1 tiles of 64 x 64.  No 16-bit type is involved: both builds
+ * behave identically. */
+int rg_tile_transform(const void* src, int src_dtype, float* dst, int N, int C, int S, const int* codes, float mean, float stdv,
+                      void* stream);
 
 /* ---- the fp32 mode on the bf16 matrix cores, operands split ONCE PER TENSOR (rna_gan_amd/csrc/rg_conv8f.hip, rg_wgrad8f.hip) ----
  * The reference computes in fp32 (src/betaVAE.py:184,223; the GAN CLI never enables AMP).  An fp32 value is the exact sum of three

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librnagan_hip.so")
 
 RG_F32, RG_BF16, RG_F16 = 0, 1, 2
-RG_U8 = 3            # a source type of rg_resize_bilinear01 only
+RG_U8 = 3            # a source type only (rg_resize_bilinear01, rg_tile_transform)
 ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA = 0, 1, 2
 
 _p = C.c_void_p
@@ -144,6 +144,7 @@ PROTOTYPES = {
     "rg_cast_pad": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "rg_selftest_layouts": (_i, [_p, _p]),
     "rg_u8_to_norm": (_i, [_p, _p, _z, _f, _f, _p]),
+    "rg_tile_transform": (_i, [_p, _i, _p, _i, _i, _i, _p, _f, _f, _p]),
     "rg_conv_up_fp8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _f, _i, _p]),
     "rg_gemm_fp8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _f, _i, _p]),
     "rg_fp8_supported": (_i, [_i, _i, _i, _i]),
@@ -198,7 +199,8 @@ PROTOTYPES = {
     "rg_probe_fill_bf16": (_i, [_p, _z, C.c_uint, _p]),
 }
 
-# must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES
+# must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES when an existing entry
+# point changes; an entry point that is only ADDED (rg_tile_transform) keeps the number -- load() refuses a library that lacks it
 ABI_VERSION = 618
 
 _libs = {}

@@ -503,7 +503,7 @@ class PatchDataset(PatchRNADataset):
 class ToFloatNormalize:
     """The reference's transform (src/histopathology_gan.py:106-109) on the host: uint8 CHW -> float / 255 -> (x - mean) /
     std.  The device-side equivalent is rg_u8_to_norm (HipOps.u8_to_norm): give the dataset ``transforms=None`` and
-    normalise the collated uint8 batch on the GPU."""
+    normalise the collated uint8 batch on the GPU (rna_gan_amd.augment.InputTransform, the CLI's --device_transform 1)."""
 
     def __init__(self, mean=0.5, std=0.5):
         self.mean, self.std = mean, std

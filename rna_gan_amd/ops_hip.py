@@ -782,6 +782,22 @@ class HipOps:
         check(self.lib.rg_u8_to_norm(_ptr(u8), _ptr(y), u8.numel(), float(mean), float(std), self.stream), "rg_u8_to_norm")
         return y
 
+    def tile_transform(self, src, codes=None, mean=0.5, std=0.5):
+        """The device-side input transform (rg_tile_transform): [N][C][S][S] uint8 or fp32 tiles -> fp32, uint8 normalised as
+        u8_to_norm (bit-identical), fp32 copied; sample n is mapped by the square symmetry ``codes[n] & 7`` (int32 device
+        tensor of N codes; None = the identity for every sample).  One launch."""
+        assert src.dim() == 4 and src.shape[2] == src.shape[3] and src.is_contiguous() and src.is_cuda
+        assert src.dtype in (torch.uint8, torch.float32)
+        N, C, S, _ = src.shape
+        if codes is not None:
+            assert codes.dtype == torch.int32 and codes.is_cuda and codes.is_contiguous() and codes.numel() == N
+        y = self._f32(N, C, S, S)
+        if N == 0:
+            return y
+        check(self.lib.rg_tile_transform(_ptr(src), _abi.RG_U8 if src.dtype == torch.uint8 else RG_F32, _ptr(y), N, C, S,
+                                         _ptr(codes), float(mean), float(std), self.stream), "rg_tile_transform")
+        return y
+
     def export_images_nhwc(self, img_nchw):
         """NCHW fp32 in [-1,1] -> NHWC fp32 in [0,1] (un-normalise + permute, src/gan_utils.py:236-241)."""
         N, C, H, W = img_nchw.shape

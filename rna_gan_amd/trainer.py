@@ -40,8 +40,11 @@ class Trainer:
     def __init__(self, models, losses_list, metrics_list=None, device=torch.device("cuda:0"), ncritic=1, epochs=5,
                  sample_size=8, checkpoints="./model/gan", retain_checkpoints=5, recon="./images", log_dir=None,
                  test_noise=None, nrow=8, precision="bf16", prefetch=True, loss_scaling="static", loss_scaling_args=None,
-                 ema_decay=None, ema_warmup=True, **kwargs):
+                 ema_decay=None, ema_warmup=True, input_transform=None, **kwargs):
         self.device = torch.device(device)
+        # the device-side input transform (rna_gan_amd.augment.InputTransform): applied to the image of every training batch
+        # in front of train_iter; None (the default) leaves the batch as the loader made it
+        self.input_transform = input_transform
         self.prefetch = bool(prefetch)          # extra knob: host batches are copied to the device one iteration ahead
         self.pipeline = bool(kwargs.pop("pipeline", True))   # extra knob: see train_iter
         self.model_names = []
@@ -154,6 +157,8 @@ class Trainer:
         if self.ema is not None:
             model["generator_ema"] = self.ema.state_dict()
             model["ema_information"] = {"decay": self.ema.decay, "warmup": self.ema.warmup}
+        if self.input_transform is not None:
+            model["input_transform"] = self.input_transform.state_dict()
         if save_items is not None:
             for it in ([save_items] if isinstance(save_items, str) else save_items):
                 model.update({it: getattr(self, it)})
@@ -200,6 +205,8 @@ class Trainer:
                 else:
                     self.ema.reset()
                     print("load_model: the checkpoint holds no averaged generator: the average restarts from the loaded generator")
+            if self.input_transform is not None and "input_transform" in checkpoint:   # (ignored when no transform is set)
+                self.input_transform.load_state_dict(checkpoint["input_transform"])
             if load_items is not None:
                 for it in ([load_items] if isinstance(load_items, str) else load_items):
                     obj = checkpoint[it]
@@ -375,6 +382,19 @@ class Trainer:
             for model, was_training in modes:
                 model.train(was_training)
 
+    def _transform_batch(self, data):
+        """The batch with its image replaced by input_transform(image, device): the tuple / list form's first entry, the bare
+        tensor, or the dict's "image" entry.  The containers are copied, never written: the loader's objects stay as they are."""
+        tf = self.input_transform
+        if isinstance(data, (tuple, list)):
+            return [tf(data[0], self.device)] + list(data[1:])
+        if isinstance(data, torch.Tensor):
+            return tf(data, self.device)
+        if isinstance(data, dict) and "image" in data:
+            data = dict(data)
+            data["image"] = tf(data["image"], self.device)
+        return data
+
     def train(self, data_loader, **kwargs):
         for name in self.model_names:
             getattr(self, name).train()
@@ -388,6 +408,8 @@ class Trainer:
             # batches arrive on the device one iteration ahead (rna_gan_amd/prefetch.py); the .to() calls below and the
             # plugins' own then find the tensors in place
             for data in (DevicePrefetcher(data_loader, self.device) if self.prefetch else data_loader):
+                if self.input_transform is not None:
+                    data = self._transform_batch(data)
                 if isinstance(data, (tuple, list)):
                     self.real_inputs = data[0].to(self.device)
                     self.labels = data[1].to(self.device)
