@@ -14,7 +14,7 @@ the gradient of the MEAN over ranks of the rank-local losses.
   403 -> 269 MB on the wire per iteration and rank.
 * Collectives are never captured into HIP graphs: for world > 1 each train_op is graph(prefix) / graph(rest) /
   eager all-reduce start, and the wait + optimizer-step graph are issued by the NEXT train_op after its prefix
-  (which reads the other network), so the transfer overlaps with compute (losses._Runner.run_dp).
+  (which reads the other network), so the transfer overlaps with compute (train_op._Runner.run_dp).
 """
 from __future__ import annotations
 

@@ -735,7 +735,7 @@ def gen_backward(ops, G: GenNet, ctx, gimg, accumulate: bool, need_input_grad: b
 # --------------------------------------------------------------------------------------------
 # Each body is split into a PREFIX that reads only one of the two networks and the REST.  A data-parallel run
 # keeps the previous train_op's gradient all-reduce and optimizer step of the OTHER network in flight while the
-# prefix executes (losses._Runner.run_dp); a single process simply runs rest(prefix()).
+# prefix executes (train_op._Runner.run_dp); a single process simply runs rest(prefix()).
 def gen_loss_prefix(ops, G, noise):
     """G(z): reads the generator only."""
     return _gen_fwd(ops, G, noise)

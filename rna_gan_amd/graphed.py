@@ -46,7 +46,7 @@ class StepGraph:
 
     ``modules``: HIP modules used by fn.  Weight re-packing is decided by Python-side version counters
     that are frozen inside a graph, so the caller keys graphs by the staleness pattern of the modules
-    (losses._Runner) and this class replays the counters' evolution after each replay: every module
+    (train_op._Runner) and this class replays the counters' evolution after each replay: every module
     used ends up freshly packed, then the ``stepped`` modules (whose optimizer ran) become stale;
     ``optimizers``: rna_gan_amd.optim.Adam instances stepped inside fn (host step mirror)."""
 
@@ -63,7 +63,7 @@ class StepGraph:
         self.calls = 0
         self.failed = False
         self._out_spec = None          # (shape, dtype, device) of every tensor the last eager run returned
-        self.wire_cell = None          # data parallel: what fn's last eager run recorded for the all-reduce (losses._Runner._dp_grads)
+        self.wire_cell = None          # data parallel: what fn's last eager run recorded for the all-reduce (train_op._Runner._dp_grads)
         self._rebuilt = {}             # fp32-storage modules: {id(module): [ConvW whose operand images the captured function rebuilds]}
 
     STABLE_NUMEL = 4096                # outputs up to this size get a home outside the graph pool

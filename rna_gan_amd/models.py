@@ -45,7 +45,7 @@ class FlatParams:
         params = [p for p in module.parameters()]
         dev = params[0].device
         # generation of this re-homing: captured HIP graphs hold the raw addresses of data / grad / shadow, so the
-        # graph cache keys carry it (losses._Runner) and a rebuilt FlatParams never replays an older graph
+        # graph cache keys carry it (train_op._Runner) and a rebuilt FlatParams never replays an older graph
         FlatParams._GEN[0] += 1
         self.gen = FlatParams._GEN[0]
         self.numel = sum(p.numel() for p in params)

@@ -248,3 +248,35 @@ def test_own_package_globals_and_placeholder_load_items_are_refused(reference_ch
         _tolerant_pickle.is_placeholder(v) for v in getattr(tr, "metric_objects", {}).values())
     tr.load_model(load_path=path, load_items="metric_logs")        # plain data passes
     assert tr.metric_logs == {"ClassifierScore": [1.0]}
+
+
+def test_a_checkpoint_that_names_losses_runner_still_loads():
+    """Loss objects are pickled into checkpoints with their graph cache object, and checkpoints written before the scheduler
+    moved to rna_gan_amd.train_op name the global ``rna_gan_amd.losses _Runner``.  Such a stream (protocol 2: GLOBAL is plain
+    text, so it is written by hand here -- NEWOBJ on an empty tuple, BUILD with the empty dict that __getstate__ returns) loads
+    to a runner with empty graph caches, through pickle and through the tolerant loader alike."""
+    import pickle
+    from rna_gan_amd import train_op
+    stream = b"\x80\x02crna_gan_amd.losses\n_Runner\nq\x00)\x81q\x01}q\x02b."
+    for loads in (pickle.loads, _tolerant_pickle.loads):
+        r = loads(stream)
+        assert type(r) is train_op._Runner and L._Runner is train_op._Runner
+        assert r._graphs == {} and r._pre == {}
+    assert ("rna_gan_amd.losses", "_Runner") not in _tolerant_pickle.missing_globals()
+
+
+def test_a_stock_loss_object_round_trips_through_the_tolerant_loader(tmp_path):
+    """What save_model writes under loss_objects today comes back through load_model's loader as the live classes: the plugin
+    with its settings, its runner a fresh train_op._Runner -- captured graphs are not state."""
+    from rna_gan_amd import train_op
+    plugins = _plugins()
+    plugins[1]._runner._graphs[("d", None)] = object()            # stands for a captured graph: must not travel
+    path = str(tmp_path / "now.model")
+    torch.save({"epoch": 1, "loss_objects": {type(p).__name__: p for p in plugins}}, path)
+    ck = torch.load(path, map_location="cpu", weights_only=False, pickle_module=_tolerant_pickle)
+    for p in plugins:
+        q = ck["loss_objects"][type(p).__name__]
+        assert type(q) is type(p) and not _tolerant_pickle.is_placeholder(q)
+        assert type(q._runner) is train_op._Runner and q._runner._graphs == {} and q._runner._pre == {}
+    assert ck["loss_objects"]["WassersteinDiscriminatorLoss"].clip == (-0.01, 0.01)
+    assert ck["loss_objects"]["WassersteinGradientPenalty"].lambd == 10.0

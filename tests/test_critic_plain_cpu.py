@@ -223,8 +223,8 @@ def test_autograd_cotangents_features_and_eval():
 
 
 def test_losses_decline_the_deferred_forms_for_the_plain_net():
-    """The deferred-slab / wire forms of rna_gan_amd.losses gate on engine.DiscNet: PlainDiscNet is not one."""
-    from rna_gan_amd import losses as L
+    """The deferred-slab / wire forms of rna_gan_amd.train_op gate on engine.DiscNet: PlainDiscNet is not one."""
+    from rna_gan_amd import train_op as L
     D2 = M.DCGANDiscriminator(32, 3, 8, batchnorm=False)
     Dn = E.build_disc_net(E.tap_major_(D2))
     assert not isinstance(Dn, (E.GenNet, E.DiscNet))

@@ -197,11 +197,11 @@ def test_check_handoffs_is_rank_collective():
 
 
 def test_dp_wire_table_tiles_the_travelling_part_of_the_flat_buffer():
-    """Host logic of the data-parallel wire-direct route (losses._dp_wire_table): what the weight-gradient launches of a pass left
+    """Host logic of the data-parallel wire-direct route (train_op._dp_wire_table): what the weight-gradient launches of a pass left
     on the layer handles -- split-K slabs (buffer, nsplit, dtype) or a slice already written to the wire (None, -1, 0) -- becomes
     a segment table that tiles flat[head:] in order, plain ranges in between; layers that left nothing stay plain; the handles
     are cleared."""
-    from rna_gan_amd import losses as PL
+    from rna_gan_amd import train_op as PL
 
     flat = torch.zeros(10000)
 
@@ -227,10 +227,10 @@ def test_dp_wire_table_tiles_the_travelling_part_of_the_flat_buffer():
 
 
 def test_armed_gradient_pass_sets_and_clears_its_flags():
-    """losses._armed, the one place a gradient pass is armed to leave weight gradients unreduced: leftovers on the armed layers
+    """train_op._armed, the one place a gradient pass is armed to leave weight gradients unreduced: leftovers on the armed layers
     are gone before the body runs; inside, every flag is set; after a normal exit every flag is back at its default and what
     the body left pending is still there (the caller consumes it); after a body that raises, nothing is pending either."""
-    from rna_gan_amd import losses as PL
+    from rna_gan_amd import train_op as PL
     from rna_gan_amd.engine import ConvW
 
     def handle():
@@ -276,3 +276,24 @@ def test_armed_gradient_pass_sets_and_clears_its_flags():
     assert all(pending(cw) == (None, None, None) for cw in armed) and other.pending_slabs == "theirs"
     with PL._armed():                                              # nothing to arm: a plain pass
         pass
+
+
+def test_the_scheduler_switches_live_on_train_op_alone():
+    """A switch is read as a train_op global at call time, so it has to be set THERE: rna_gan_amd.losses re-exports none of them
+    (setting an attribute on a module never fails -- a stale ``losses.G0_ADAM = False`` would silently do nothing) except
+    DP_ROUTE, which bench.py reads once for its config record.  The two switches that nothing selected are gone."""
+    import os
+    import rna_gan_amd
+    from rna_gan_amd import losses, train_op
+    switches = {n for n, v in vars(train_op).items() if n.isupper() and not n.startswith("_") and isinstance(v, (bool, int, str))}
+    assert {"G0_ADAM", "SLAB_ADAM", "SKINNY_SLAB_ADAM", "DP_ROUTE", "DP_PREFIX_MODE", "DP_PREFIX_BWD", "OVERLAP", "FUSED_WIDEN",
+            "DP_WIRE_DIRECT"} <= switches
+    for name in switches:
+        assert hasattr(train_op, name)
+        assert hasattr(losses, name) == (name == "DP_ROUTE"), name
+    pkg = os.path.dirname(rna_gan_amd.__file__)
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith((".py", ".hip", ".h")):
+                text = open(os.path.join(dirpath, f), errors="replace").read()
+                assert "RNAGAN_D_BATCHED" not in text and "RNAGAN_FAKE_LOOKAHEAD" not in text, f

@@ -1,7 +1,7 @@
 """The data-parallel path at WORLD SIZE 2 on real kernels.  The GPU box has one device, and RCCL refuses two
 ranks on one device, so the two rank processes share cuda:0 and all-reduce over gloo (which stages device tensors through
 the host): everything else is the product's DP route exactly as an 8-GPU run takes it -- the loss plugins' step() ->
-losses._Runner.run_dp: graph(prefix) / flush of the pending optimizer step / graph(rest) / gradient all-reduce started
+train_op._Runner.run_dp: graph(prefix) / flush of the pending optimizer step / graph(rest) / gradient all-reduce started
 eagerly, the optimizer step applied by the NEXT train_op after its prefix, 1/world folded into the backward seed, rank-local
 BatchNorm statistics, the D-loss prefix = D(real) forward + backward.
 

@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 from oracle import ref_cpu as R
 import rna_gan_amd as P
 from rna_gan_amd import losses as PL
+from rna_gan_amd import train_op as TO
 
 DIGEST_OVER = 20000
 
@@ -613,10 +614,10 @@ def test_generator_layer0_gradient_inside_the_adam_step(in_size, enc, n):
     D0 = R.seeded_fill_(R.OracleDCGANDiscriminator(in_size, 3, step, nonlinearity=nn.LeakyReLU(0.2),
                                                    last_nonlinearity=nn.LeakyReLU(0.2)), 8)
     res = []
-    keep = PL.G0_ADAM
+    keep = TO.G0_ADAM
     try:
         for fused in (True, False):
-            PL.G0_ADAM = fused
+            TO.G0_ADAM = fused
             G, D, og, od = product_pair(in_size, step, enc, "bf16", G0, D0)
             lg = PL.WassersteinGeneratorLoss()
             losses = []
@@ -630,7 +631,7 @@ def test_generator_layer0_gradient_inside_the_adam_step(in_size, enc, n):
                         st["exp_avg_sq"].float().cpu().clone(), G.flat.shadow[:G.model[0][0].weight.numel()].float().cpu().clone(),
                         {k: v.detach().float().cpu().clone() for k, v in G.state_dict().items()}))
     finally:
-        PL.G0_ADAM = keep
+        TO.G0_ADAM = keep
     (la, wa, ma, va, sa, sda), (lb, wb, mb, vb, sb, sdb) = res
     w0 = G0.model[0][0].weight.detach()
     assert max(abs(x - y) / (abs(y) + 0.1) for x, y in zip(la, lb)) < 2e-3, (la, lb)

@@ -16,8 +16,8 @@ A variant is  name:key=value,key=value ...  with keys of three kinds
     (they only act when a launch is issued eagerly or captured; a captured graph replays what it captured);
   * RNAGAN_* environment variables that the host side reads when a workload is built (HipOps / Adam construction),
     exported before the variant is built and restored afterwards;
-  * the module-level switches of rna_gan_amd.losses (LOOKAHEAD, D_BATCHED, G0_ADAM, ...), written as losses.NAME=0/1 and
-    re-applied at every switch.
+  * module-level switches, written as <module>.NAME=value for the modules rna_gan_amd.train_op (the scheduler's: G0_ADAM,
+    SLAB_ADAM, DP_ROUTE, ...) and rna_gan_amd.losses (LATENT_CACHE), re-applied at every switch; an unknown NAME is an error.
 Nothing here is imported by the product or the tests.
 """
 import argparse
@@ -50,29 +50,37 @@ def parse_variants(spec):
     return out
 
 
+def _switch(key):
+    """"<module>.NAME" -> (rna_gan_amd.<module>, NAME) for getattr / setattr; an unknown module or NAME is an error."""
+    from rna_gan_amd import losses, train_op
+    mod, _, name = key.partition(".")
+    mod = {"losses": losses, "train_op": train_op}[mod]
+    getattr(mod, name)
+    return mod, name
+
+
 class Variant:
     def __init__(self, name, kv, lib):
         self.name, self.lib = name, lib
-        self.copts = {k: int(v) for k, v in kv.items() if not k.startswith("RNAGAN_") and not k.startswith("losses.")}
+        self.copts = {k: int(v) for k, v in kv.items() if not k.startswith("RNAGAN_") and "." not in k}
         self.env = {k: v for k, v in kv.items() if k.startswith("RNAGAN_")}
-        self.mod = {k.split(".", 1)[1]: v for k, v in kv.items() if k.startswith("losses.")}
+        self.mod = {k: v for k, v in kv.items() if not k.startswith("RNAGAN_") and "." in k}      # "<module>.NAME": value
         self.step = self.flush = None
         self.times = []
 
     def apply(self, all_copts):
-        from rna_gan_amd import _abi, losses
+        from rna_gan_amd import _abi
         for k in all_copts:                                   # every option any variant names: set or cleared
             _abi.check(self.lib.rg_set_option(k.encode(), self.copts.get(k, -1)), "rg_set_option(%s)" % k)
         for k, v in self.mod.items():
-            cur = getattr(losses, k)
-            setattr(losses, k, type(cur)(int(v)) if not isinstance(cur, str) else v)
+            cur = getattr(*_switch(k))
+            setattr(*_switch(k), type(cur)(int(v)) if not isinstance(cur, str) else v)
 
     def build(self, bench, args, device, all_copts, base_mod):
-        from rna_gan_amd import losses
         saved = {k: os.environ.get(k) for k in self.env}
         os.environ.update(self.env)
         for k, v in base_mod.items():
-            setattr(losses, k, v)
+            setattr(*_switch(k), v)
         self.apply(all_copts)
         try:
             self.step, self.flush, self.n, self.info = bench.hip_workload(args, 0, 1, device)
@@ -105,7 +113,7 @@ def main():
                          "configured workloads in one process differ by 0.006 ... 0.12 ms (buffer placement), DESIGN 14.1")
     a = ap.parse_args()
     import bench
-    from rna_gan_amd import _abi, losses
+    from rna_gan_amd import _abi
     lib = _abi.load()
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
@@ -119,7 +127,7 @@ def main():
     vs = [Variant(n, kv, lib) for n, kv in pv]
     assert len(vs) >= 2, "need at least two variants"
     all_copts = sorted({k for v in vs for k in v.copts})
-    base_mod = {k: getattr(losses, k) for v in vs for k in v.mod}
+    base_mod = {k: getattr(*_switch(k)) for v in vs for k in v.mod}
     for v in vs:
         t0 = time.perf_counter()
         v.build(bench, bargs, device, all_copts, base_mod)
@@ -127,7 +135,7 @@ def main():
     for r in range(a.rounds):
         for v in (vs if r % 2 == 0 else vs[::-1]):           # alternate the order inside a round too
             for k, val in base_mod.items():
-                setattr(losses, k, val)
+                setattr(*_switch(k), val)
             v.apply(all_copts)
             for _ in range(a.warmup):
                 v.step()
@@ -147,7 +155,7 @@ def main():
     base = vs[0]
     for v in vs:
         d = [x - y for x, y in zip(v.times, base.times)]
-        res["variants"].append({"name": v.name, "options": dict(v.copts, **v.env, **{"losses." + k: x for k, x in v.mod.items()}),
+        res["variants"].append({"name": v.name, "options": dict(v.copts, **v.env, **v.mod),
                                 "ms": [round(x, 3) for x in v.times], "mean": round(sum(v.times) / len(v.times), 3),
                                 "min": round(min(v.times), 3),
                                 "delta_vs_first": {"mean": round(sum(d) / len(d), 3), "min": round(min(d), 3),
