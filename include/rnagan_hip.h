@@ -830,6 +830,28 @@ int rg_u8_to_norm(const void* src_u8, float* dst, size_t n, float mean, float st
 int rg_tile_transform(const void* src, int src_dtype, float* dst, int N, int C, int S, const int* codes, float mean, float stdv,
                       void* stream);
 
+/* The device-side tile export (rna_gan_amd.export; rna_gan_amd/csrc/rg_export.hip): generated images -> uint8 tiles, quantised and
+ * laid out in one launch, so a batch leaves the device as C bytes per pixel instead of 4 C.
+ *   src   [N][C][H][W] fp32;  dst N C H W bytes
+ *   flags RG_EXPORT_PLANAR   clear: dst [N][H][W][C], interleaved (a PNG, a tile record);  set: dst [N][C][H][W]
+ *         RG_EXPORT_REVERSE  destination channel c takes source channel C - 1 - c (BGR for C = 3, the order of the tile records)
+ *         RG_EXPORT_TRUNC    clear: the rounding rule;  set: the truncating rule
+ *   value every step a separately rounded fp32 operation, no contraction, a true division, no reciprocal:
+ *           v = (x - sub) / div      ((sub, div) = (-1, 2): bit for bit the value of rg_export_images_nhwc;
+ *                                     (lo, max(hi - lo, 1e-5)): the min-max normalisation of an image grid)
+ *           t = v * 255.0f + 0.5f    rounding rule (torchvision save_image's mul(255).add_(0.5));   t = v * 255.0f  truncating rule
+ *           byte = 0 if !(t >= 0) (NaN and -0.0 included), 255 if t >= 255, otherwise t truncated toward zero
+ * Any N >= 0, C >= 1, H, W >= 1; no workspace; src needs 4-byte and dst 1-byte alignment only (C == 3, W % 4 == 0, or the planar
+ * layout with H W % 4 == 0, with a 16-byte-aligned src and a 4-byte-aligned dst take the vector paths, same bytes).  Nothing
+ * outside the two tensors is read or written; they must not overlap.  No host synchronisation, no allocation, safe under graph
+ * capture, any stream.  N == 0: RG_OK, nothing launched.  RG_EINVAL (nothing launched) for a NULL buffer, N < 0, C, H or W <= 0,
+ * div == 0 or NaN, or an unknown flag bit; RG_EUNSUPPORTED for more than 2^31 - 1 workgroups.  No 16-bit type is involved: both
+ * builds behave identically. */
+#define RG_EXPORT_PLANAR 1
+#define RG_EXPORT_REVERSE 2
+#define RG_EXPORT_TRUNC 4
+int rg_tile_export_u8(const float* src, uint8_t* dst, int N, int C, int H, int W, float sub, float div, int flags, void* stream);
+
 /* ---- the fp32 mode on the bf16 matrix cores, operands split ONCE PER TENSOR (rna_gan_amd/csrc/rg_conv8f.hip, rg_wgrad8f.hip) ----
  * The reference computes in fp32 (src/betaVAE.py:184,223; the GAN CLI never enables AMP).  An fp32 value is the exact sum of three
  * bf16 numbers v = h + m + l; rg_split_planes writes them as a plane-major buffer planes[3][n] (bf16, n % 8 == 0) in one

@@ -12,7 +12,8 @@ RNA table preparation, restated without the packages that are absent here.
   FLG / BD / header checksum, independent or linked blocks, stored blocks, optional content size / block / content
   checksums -- checksums are skipped, not verified: xxHash32 is only needed to WRITE a header) and the LZ4 block format
   (token, literal / match lengths with 255-continuation, 2-byte little-endian offsets, overlapping copies);
-  ``lz4f_compress`` writes valid frames (greedy hash-chain matcher, 64 KB independent blocks).  Parity with the
+  ``lz4f_compress`` writes valid frames (greedy hash-chain matcher, 64 KB independent blocks; ``stored=True``: uncompressed
+  blocks, for writers that sit behind the device-side tile export).  Parity with the
   lz4framed package itself is unpinned (not installable here); the decoder is tested on hand-assembled frames.
 * **RNA table** (src/histopathology_gan.py:131-151): natural log with zeros kept at 0, columns reordered to
   [rna_*, others], StandardScaler over the rna_ columns (population standard deviation, constant columns scaled by 1).
@@ -211,10 +212,13 @@ def lz4_block_compress(src: bytes) -> bytes:
     return bytes(out)
 
 
-def lz4f_compress(data: bytes, block_size: int = 1 << 16) -> bytes:
+def lz4f_compress(data: bytes, block_size: int = 1 << 16, stored: bool = False) -> bytes:
     """bytes -> LZ4 frame (independent blocks of one of the format's four sizes, 64 KB by default, no checksums besides
     the mandatory header byte, content size recorded): readable by any LZ4 frame decoder -- checked against liblz4's
-    LZ4F_decompress, the call lz4framed.decompress makes (tests/test_lz4_system_cpu.py)."""
+    LZ4F_decompress, the call lz4framed.decompress makes (tests/test_lz4_system_cpu.py).
+    stored=True: every block is written UNCOMPRESSED (the high bit of its size set), same header: the matcher below is pure
+    Python and far too slow behind a device that emits thousands of tiles per second; the format allows such blocks and
+    every decoder reads them."""
     code = {1 << 16: 4, 1 << 18: 5, 1 << 20: 6, 1 << 22: 7}.get(block_size)
     if code is None:
         raise ValueError("lz4f: block size must be 64 KB, 256 KB, 1 MB or 4 MB")
@@ -224,7 +228,7 @@ def lz4f_compress(data: bytes, block_size: int = 1 << 16) -> bytes:
     out = bytearray(struct.pack("<I", LZ4F_MAGIC) + desc + bytes([(_xxh32(desc) >> 8) & 0xFF]))
     for off in range(0, len(data), block_size):
         chunk = data[off:off + block_size]
-        comp = lz4_block_compress(chunk) if len(chunk) > 16 else None
+        comp = lz4_block_compress(chunk) if len(chunk) > 16 and not stored else None
         if comp is not None and len(comp) < len(chunk):
             out += struct.pack("<I", len(comp)) + comp
         else:
@@ -236,15 +240,15 @@ def lz4f_compress(data: bytes, block_size: int = 1 << 16) -> bytes:
 # ------------------------------------------------------------------------------------------------------------------
 # tile records
 # ------------------------------------------------------------------------------------------------------------------
-def serialize_and_compress(obj) -> bytes:
-    """src/preprocess/patch_gen_grid.py:145-146."""
-    return lz4f_compress(pickle.dumps(obj))
+def serialize_and_compress(obj, stored: bool = False) -> bytes:
+    """src/preprocess/patch_gen_grid.py:145-146.  stored: see lz4f_compress."""
+    return lz4f_compress(pickle.dumps(obj), stored=stored)
 
 
-def encode_record(name: str, image_hwc_u8: np.ndarray) -> bytes:
+def encode_record(name: str, image_hwc_u8: np.ndarray, stored: bool = False) -> bytes:
     """Value of one tile key (src/preprocess/patch_gen_grid.py:129-132): (name, raw bytes, shape)."""
     image = np.ascontiguousarray(image_hwc_u8, dtype=np.uint8)
-    return serialize_and_compress((name, image.tobytes(), image.shape))
+    return serialize_and_compress((name, image.tobytes(), image.shape), stored=stored)
 
 
 def encode_keys(n: int) -> bytes:
@@ -323,13 +327,20 @@ def open_tile_store(path):
         return LmdbReadOnly(path)
 
 
-def write_tile_store(path: str, tiles_hwc_u8, slide_id: str = "slide"):
-    """Directory store with the reference's record format (keys b"0".., b"__keys__")."""
+def write_tile_store(path: str, tiles_hwc_u8, slide_id: str = "slide", stored: bool = False, channel_order: str = "bgr"):
+    """Directory store with the reference's record format (keys b"0".., b"__keys__").
+    channel_order states what the tiles handed in ARE: "bgr" (the default, the order of the reference's records) writes them as
+    given; "rgb" reverses the channels before encoding, so that the reader (decompress_and_deserialize, which swaps them
+    back) returns what was handed in.  stored: records as uncompressed LZ4-frame blocks (lz4f_compress)."""
+    if channel_order not in ("bgr", "rgb"):
+        raise ValueError("channel_order must be 'bgr' or 'rgb'")
     os.makedirs(path, exist_ok=True)
     n = 0
     for i, tile in enumerate(tiles_hwc_u8):
+        if channel_order == "rgb":
+            tile = np.asarray(tile)[:, :, ::-1]
         with open(os.path.join(path, str(i)), "wb") as f:
-            f.write(encode_record("{0}_patch_{1}".format(slide_id, i), tile))
+            f.write(encode_record("{0}_patch_{1}".format(slide_id, i), tile, stored=stored))
         n += 1
     with open(os.path.join(path, "__keys__"), "wb") as f:
         f.write(encode_keys(n))
