@@ -18,6 +18,13 @@ which it never defines, and needs cv2 and matplotlib); two modes work here:
 Both run through rna_gan_amd.gan_utils.generate_tiles: the tiles are quantised and interleaved on the device
 (rg_tile_export_u8) and cross the host link as uint8 behind a double-buffered pinned download.
 
+--qc report|filter (bulk mode) holds the generated tiles to the acceptance rule of the reference's tiler (rna_gan_amd.tissue: the
+tissue mask, dilated --qc_dilate times, covers more than --qc_min_tissue of the tile and the tile is not low-contrast).  The rule runs on the uint8
+chunk where it lies on the device; 12 integers per tile travel with the chunk.  report writes D/qc.csv (one row per tile: patient,
+tile, stored_index, the four Otsu thresholds, tissue_fraction, the two luma percentiles, low_contrast, accepted); filter also
+leaves the rejected tiles out of the output (the kept ones are renumbered in tile order; stored_index names them, -1 = left out)
+and prints how many per patient.  off (the default) runs none of it: every output byte is as without the flag.
+
 Extra flags: --prepare_rna 1 (log_standardize_rna over the file's rows first), --quantize round|trunc (trunc reproduces the
 reference script's ``img *= 255; astype(uint8)``; round returns a tile that went through the input transform unchanged),
 --g_ema 1 (the checkpoint's averaged generator), --fp8 1, --chunk, --group, --seed, --precision; --synthetic runs on seeded random
@@ -61,7 +68,13 @@ EXTRA_FLAGS = [
     ("--seed", int, 0, "seed of the private uniform draw (and of --random_patient's row choice)"),
     ("--precision", str, "bf16", "bf16, fp16 or fp32"),
     ("--img_size", int, 256, "--synthetic: tile edge"),
+    ("--qc", str, "off", "bulk mode: off, report (write qc.csv beside the output) or filter (also leave rejected tiles out)"),
+    ("--qc_min_tissue", float, 0.2, "--qc: the dilated tissue mask must cover MORE than this fraction of a tile"),
+    ("--qc_dilate", int, 3, "--qc: iterations of the 4-connected dilation of the tissue mask (0..8; the reference tiler's 3)"),
+    ("--qc_rgb_min", int, 50, "--qc: a tissue pixel has R, G and B above this (0..255; the reference tiler's 50)"),
 ]
+QC_COLUMNS = ("patient", "tile", "stored_index", "otsu_r", "otsu_g", "otsu_b", "otsu_s", "tissue_fraction", "luma_p1", "luma_p99",
+              "low_contrast", "accepted")
 
 
 def parse_args(argv=None):
@@ -92,6 +105,14 @@ def parse_args(argv=None):
             ap.error("--out_format must be store, png or npy")
         if not args.patients.strip():
             ap.error("--patients must be all or a comma list")
+    if args.qc not in ("off", "report", "filter"):
+        ap.error("--qc must be off, report or filter")
+    if args.qc != "off" and args.random_patient:
+        ap.error("--qc belongs to bulk mode")
+    if not 0.0 <= args.qc_min_tissue <= 1.0:
+        ap.error("--qc_min_tissue must be in [0, 1]")
+    if not 0 <= args.qc_dilate <= 8 or not 0 <= args.qc_rgb_min <= 255:
+        ap.error("--qc_dilate must be in 0..8 and --qc_rgb_min in 0..255")
     if not args.synthetic:
         for flag in ("checkpoint", "rna_file", "vae_checkpoint"):
             if getattr(args, flag) is None:
@@ -215,12 +236,28 @@ def run(args, trainer=None, betavae=None):
     os.makedirs(args.out_dir, exist_ok=True)
     names = [ids[i] for i in sel]
     written = []
+    qc_on = args.qc != "off"
+    qc_rows = {}                  # (patient, tile) -> (12 integers, tissue fraction, percentiles, low_contrast, accepted)
     # tile-major walk: a patient's tiles arrive spread over the whole run.  png files are written as they arrive; store and npy
     # collect one (T, H, W, 3) array per patient (3 bytes per pixel on the host)
     per_patient = {}
-    for p, t, a in generate_tiles(trainer, rows[sel], T, betavae, **common):
+    qc = dict(dilate=args.qc_dilate, rgb_min=args.qc_rgb_min) if qc_on else None
+    for item in generate_tiles(trainer, rows[sel], T, betavae, qc=qc, **common):
+        p, t, a = item[0], item[1], item[2]
+        keep = np.ones(a.shape[0], dtype=bool)
+        if qc_on:
+            from rna_gan_amd import tissue as TQ
+            st = TQ.stats_from_rows(item[3], a.shape[1], a.shape[2], **qc)
+            ok = TQ.accept(st, min_tissue=args.qc_min_tissue)
+            frac, pct, low = TQ.tissue_fraction(st), TQ.luma_percentiles(st), TQ.low_contrast(st)
+            for k in range(a.shape[0]):
+                qc_rows[(int(p[k]), int(t[k]))] = (st.stats[k].copy(), float(frac[k]), pct[k].copy(), bool(low[k]), bool(ok[k]))
+            if args.qc == "filter":
+                keep = ok
         if args.out_format == "png":
             for k in range(a.shape[0]):
+                if not keep[k]:
+                    continue
                 d = os.path.join(args.out_dir, names[p[k]])
                 os.makedirs(d, exist_ok=True)
                 path = os.path.join(d, "%d.png" % t[k])
@@ -232,6 +269,15 @@ def run(args, trainer=None, betavae=None):
                     per_patient[q] = np.empty((T,) + a.shape[1:], dtype=np.uint8)
                 m = p == q
                 per_patient[q][t[m]] = a[m]
+    stored_index = {}
+    for q in range(len(sel)):
+        kept = [t for t in range(T) if args.qc != "filter" or qc_rows[(q, t)][4]]
+        # png files keep their tile number as their name; store and npy renumber what is kept
+        stored_index.update({(q, t): (t if args.out_format == "png" else i) for i, t in enumerate(kept)})
+        if args.qc == "filter":
+            print("patient %s: %d of %d tiles rejected" % (names[q], T - len(kept), T))
+            if q in per_patient:
+                per_patient[q] = per_patient[q][kept]
     for q, tiles in sorted(per_patient.items()):
         if args.out_format == "store":
             # where PatchDataset(patch_data_path=out_dir) looks for the slide named <id> (rna_gan_amd/data.py)
@@ -240,6 +286,15 @@ def run(args, trainer=None, betavae=None):
         else:
             path = os.path.join(args.out_dir, names[q] + ".npy")
             np.save(path, tiles)
+        written.append(path)
+    if qc_on:
+        path = os.path.join(args.out_dir, "qc.csv")
+        with open(path, "w") as f:
+            f.write(",".join(QC_COLUMNS) + "\n")
+            for (q, t) in sorted(qc_rows):
+                row, frac, pct, low, ok = qc_rows[(q, t)]
+                f.write("%s,%d,%d,%d,%d,%d,%d,%r,%r,%r,%d,%d\n" % (names[q], t, stored_index.get((q, t), -1), row[0], row[1], row[2],
+                                                                  row[3], frac, float(pct[0]), float(pct[1]), low, ok))
         written.append(path)
     return written
 

@@ -99,6 +99,10 @@ EXTRA_FLAGS = [
     ("--pr_k", int, 5, "--pr_samples: the neighbourhood size k (1..16)"),
     ("--pr_report", str, "recall", "--pr_samples: which of precision, recall, density, coverage is logged in metric_logs (all "
                                    "four are kept per epoch in the checkpointed metric's history)"),
+    ("--qc_samples", int, 0, "evaluate the tissue yield (rna_gan_amd.metrics.TissueYield) after every epoch: the fraction of N "
+                             "generated tiles that the reference tiler's acceptance rule keeps -- a tissue mask over more than "
+                             "20 % of the tile, not low-contrast (rna_gan_amd.tissue, on the device; no real tiles are judged); "
+                             "with another metric over N samples it shares the noise (0 = off)"),
     ("--device_transform", int, 0, "1 = the loader hands over uint8 tiles (a quarter of the host-to-device bytes) and one launch "
                                    "normalises them on the device, bit-identical to the host transform "
                                    "(rna_gan_amd.augment.InputTransform); 0 = the reference's host transform"),
@@ -157,6 +161,8 @@ def parse_args(argv=None):
         ap.error("--pr_k must be in 1..16")
     if args.pr_samples < 0 or 0 < args.pr_samples <= args.pr_k:
         ap.error("--pr_samples must be 0 (off) or at least --pr_k + 1 (a k-th neighbour needs k other samples)")
+    if args.qc_samples < 0 or args.qc_samples == 1:
+        ap.error("--qc_samples must be 0 (off) or at least 2")
     if args.pr_report not in ("precision", "recall", "density", "coverage"):
         ap.error("--pr_report must be precision, recall, density or coverage")
     if args.device_transform not in (0, 1):
@@ -231,6 +237,15 @@ def build_kid_metric(args, ds, losses, device, holder):
     real, extractor, noise, batch = metric_inputs(args, args.kid_samples, "--kid_samples", ds, losses, device, holder)
     return KernelDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch,
                           num_subsets=args.kid_subsets, subset_size=args.kid_subset_size)
+
+
+def build_qc_metric(args, ds, losses, device, holder):
+    """--qc_samples: the tissue yield of N generated tiles.  The metric judges no real tile; metric_inputs supplies the noise
+    (wganvae: built from the RNA rows of the first N items, shared with the other metrics over N samples) and the number of
+    readable items, which is the number of generated tiles."""
+    from rna_gan_amd.metrics import TissueYield
+    real, _extractor, noise, batch = metric_inputs(args, args.qc_samples, "--qc_samples", ds, losses, device, holder)
+    return TissueYield(int(real.shape[0]), noise=noise, seed=args.seed, batch_size=batch)
 
 
 def build_pr_metric(args, ds, losses, device, holder):
@@ -344,6 +359,8 @@ def main():
             metrics.append(build_kid_metric(args, ds, losses, device, holder))
         if args.pr_samples > 0:
             metrics.append(build_pr_metric(args, ds, losses, device, holder))
+        if args.qc_samples > 0:
+            metrics.append(build_qc_metric(args, ds, losses, device, holder))
     metrics = metrics or None
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,

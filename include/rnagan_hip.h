@@ -852,6 +852,40 @@ int rg_tile_transform(const void* src, int src_dtype, float* dst, int N, int C, 
 #define RG_EXPORT_TRUNC 4
 int rg_tile_export_u8(const float* src, uint8_t* dst, int N, int C, int H, int W, float sub, float div, int flags, void* stream);
 
+/* Tile quality control on the device (rna_gan_amd.tissue; rna_gan_amd/csrc/rg_tissue.hip): what a tiler's acceptance rule needs to
+ * know about a uint8 RGB tile -- Otsu thresholds, the tissue mask's coverage, luma percentiles -- as INTEGERS, so every value is
+ * exact; fractions, percentile interpolation and the accept / low-contrast decisions are made on the host from them.
+ *   tiles  N tiles of H x W pixels, 3 channels, uint8.  flags: RG_EXPORT_PLANAR clear: [N][H][W][3], set: [N][3][H][W];
+ *          RG_EXPORT_REVERSE: the stored channel order is B, G, R.  No other bit.
+ * Per tile, nothing shared between tiles:
+ *   histograms  256 bins each of R, G, B and of s8 = (255 * (mx - mn)) / mx (integer division; 0 where mx == 0), mx / mn the
+ *               pixel's largest / smallest channel: the HSV saturation on a fixed 8-bit grid.
+ *   Otsu        on an integer histogram h: lo / hi the smallest / largest occupied bin, n = sum h, S = sum i h[i].  For every
+ *               split k = lo .. hi - 1, in exactly this sequence of separately rounded fp64 operations (no contraction):
+ *                 w1 = sum_{i <= k} h[i], w2 = n - w1, s1 = sum_{i <= k} i h[i], s2 = S - s1         (integers)
+ *                 m1 = (double)s1 / (double)w1;  m2 = (double)s2 / (double)w2;  d = m1 - m2;
+ *                 v = (((double)w1 * (double)w2) * d) * d;
+ *               the threshold is the FIRST k with the largest v; lo == hi (a constant channel): the threshold is lo.
+ *               Four thresholds tR, tG, tB, tS.
+ *   raw mask    m = (s8 > tS) && !(R > tR && G > tG && B > tB) && R > rgb_min && G > rgb_min && B > rgb_min
+ *   dilation    `dilate` (0..8) iterations of the 4-connected cross, background outside the tile: a pixel is set iff some raw-mask
+ *               pixel lies within L1 distance `dilate` of it.
+ *   luma        L = 2125 R + 7154 G + 721 B (<= 2 550 000); for each of the four ranks4[j] in [0, H W) the exact order statistic:
+ *               the value at index ranks4[j] of the tile's ascending sorted L (a two-level histogram selection, no sort).
+ *   stats  int32 [N][12]: tR, tG, tB, tS, raw_count, dilated_count, L[rank 0..3], 0, 0
+ *   mask   NULL, or uint8 [N][H][W] that receives the dilated mask as 0 / 1.
+ * ranks4: FOUR HOST ints, read before the launch.  workspace: rg_tile_qc_workspace_bytes(N, H, W) bytes of device memory, 4-byte
+ * aligned, any content: the call zeroes what it accumulates into, so calling again on the same workspace gives the same answer.
+ * Five launches on `stream`; the tile bytes are read twice.  No host synchronisation, no allocation, safe under
+ * graph capture.  The results do not depend on N or on the other tiles.  N == 0: RG_OK, nothing launched.  RG_EINVAL (nothing
+ * launched) for a NULL tiles / ranks4 / stats / workspace, N < 0, H or W <= 0, an unknown flag bit, rgb_min outside 0..255, dilate
+ * outside 0..8, a rank outside [0, H W), misaligned stats / workspace, a short workspace; RG_EUNSUPPORTED for H W > 2^26 (beyond it
+ * w1 w2 would no longer be exact in fp64) or more than 2^31 - 1 workgroups.  No 16-bit type is involved: both builds behave
+ * identically. */
+size_t rg_tile_qc_workspace_bytes(int N, int H, int W);
+int rg_tile_qc(const uint8_t* tiles, int N, int H, int W, int flags, int rgb_min, int dilate, const int* ranks4, int32_t* stats,
+               uint8_t* mask_or_null, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the fp32 mode on the bf16 matrix cores, operands split ONCE PER TENSOR (rna_gan_amd/csrc/rg_conv8f.hip, rg_wgrad8f.hip) ----
  * The reference computes in fp32 (src/betaVAE.py:184,223; the GAN CLI never enables AMP).  An fp32 value is the exact sum of three
  * bf16 numbers v = h + m + l; rg_split_planes writes them as a plane-major buffer planes[3][n] (bf16, n % 8 == 0) in one

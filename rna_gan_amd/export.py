@@ -88,7 +88,7 @@ def tiles_u8(images, layout="nhwc", order="rgb", rounding="round", sub=-1.0, div
     return out
 
 
-def synthesize_u8(generator, noise, chunk=512, fp8=False, synth_chunk=None, **export_kwargs):
+def synthesize_u8(generator, noise, chunk=512, fp8=False, synth_chunk=None, qc=None, **export_kwargs):
     """Bulk synthesis delivered to the host as uint8: a generator function over ``(start, array)``, where ``array`` is a uint8
     numpy VIEW of a pinned buffer holding the tiles of noise rows start .. start + len(array) (at most ``chunk``), laid out as
     ``tiles_u8(..., **export_kwargs)`` lays them out.
@@ -98,7 +98,11 @@ def synthesize_u8(generator, noise, chunk=512, fp8=False, synth_chunk=None, **ex
     ADVANCED AGAIN: the next chunk but one lands in the same slot.  Copy what must be kept (``synthesize_u8_all`` does).
     ``noise``: (N, E) on a CUDA device.  synth_chunk: rows per ``synthesize`` call (default: ``chunk``) -- the conv kernels pick
     their tiling by batch size, so a caller whose bytes must not depend on ``chunk`` fixes this and lets ``chunk`` cut the export
-    and the download only (``generate_tiles`` does).  Draws no random numbers."""
+    and the download only (``generate_tiles`` does).  Draws no random numbers.
+    qc: None, or a dict of ``tissue.tile_stats`` settings (rgb_min, dilate, percentiles; {} for the defaults): tile quality control
+    runs on each uint8 chunk where it lies on the device (rg_tile_qc) and its 12 int32 per tile travel behind the chunk; the
+    generator then yields ``(start, array, rows)``, ``rows`` an int32 (len(array), 12) numpy VIEW valid as long as ``array`` is
+    (``tissue.stats_from_rows`` makes a TileStats of it)."""
     from .gan_utils import synthesize
     layout = export_kwargs.get("layout", "nhwc")
     export_flags(layout, export_kwargs.get("order", "rgb"), export_kwargs.get("rounding", "round"))
@@ -110,6 +114,11 @@ def synthesize_u8(generator, noise, chunk=512, fp8=False, synth_chunk=None, **ex
     synth = chunk if synth_chunk is None else int(synth_chunk)
     if chunk < 1 or synth < 1:
         raise ValueError("chunk and synth_chunk must be >= 1")
+    if qc is not None:
+        from .tissue import tile_stats_device
+        if set(qc) - {"rgb_min", "dilate", "percentiles"}:
+            raise ValueError("qc takes rgb_min, dilate and percentiles")
+        qc = dict(qc, layout=layout, order=export_kwargs.get("order", "rgb"))
     device = noise.device
     N = noise.shape[0]
     main = torch.cuda.current_stream(device)
@@ -117,6 +126,7 @@ def synthesize_u8(generator, noise, chunk=512, fp8=False, synth_chunk=None, **ex
     events = [torch.cuda.Event(), torch.cuda.Event()]
     dev = [None, None]            # device uint8 staging, one per slot
     pinned = [None, None]
+    dev_rows, pinned_rows = [None, None], [None, None]        # qc: the stats rows of a slot
     pending = None                # (start, n, slot) of the chunk whose copy is in flight
     k = 0
     for b0 in range(0, N, synth):
@@ -129,27 +139,40 @@ def synthesize_u8(generator, noise, chunk=512, fp8=False, synth_chunk=None, **ex
                 shape = _out_shape((min(chunk, synth, N),) + tuple(img.shape[1:]), layout)
                 dev[s] = torch.empty(shape, dtype=torch.uint8, device=device)
                 pinned[s] = torch.empty(shape, dtype=torch.uint8).pin_memory()
+                if qc is not None:
+                    dev_rows[s] = torch.empty((shape[0], 12), dtype=torch.int32, device=device)
+                    pinned_rows[s] = torch.empty((shape[0], 12), dtype=torch.int32).pin_memory()
             else:
                 main.wait_event(events[s])        # the copy that read this device slot (two chunks ago) is done before it is rewritten
             tiles_u8(piece, out=dev[s][:n], **export_kwargs)
+            if qc is not None:
+                tile_stats_device(dev[s][:n], out=dev_rows[s][:n], **qc)
             copy.wait_stream(main)
             with torch.cuda.stream(copy):
                 pinned[s][:n].copy_(dev[s][:n], non_blocking=True)
+                if qc is not None:
+                    pinned_rows[s][:n].copy_(dev_rows[s][:n], non_blocking=True)
                 events[s].record(copy)
             if pending is not None:
-                ps, pn, pslot = pending
-                events[pslot].synchronize()
-                yield ps, pinned[pslot][:pn].numpy()
+                yield _delivered(pending, events, pinned, pinned_rows, qc)
             pending = (b0 + c0, n, s)
     if pending is not None:
-        ps, pn, pslot = pending
-        events[pslot].synchronize()
-        yield ps, pinned[pslot][:pn].numpy()
+        yield _delivered(pending, events, pinned, pinned_rows, qc)
+
+
+def _delivered(pending, events, pinned, pinned_rows, qc):
+    ps, pn, pslot = pending
+    events[pslot].synchronize()
+    if qc is None:
+        return ps, pinned[pslot][:pn].numpy()
+    return ps, pinned[pslot][:pn].numpy(), pinned_rows[pslot][:pn].numpy()
 
 
 def synthesize_u8_all(generator, noise, chunk=512, fp8=False, synth_chunk=None, **export_kwargs):
     """The chunks of ``synthesize_u8`` copied into ONE numpy array that owns its memory."""
     out = None
+    if "qc" in export_kwargs:
+        raise ValueError("synthesize_u8_all returns the tiles alone: qc= is not accepted")
     for start, a in synthesize_u8(generator, noise, chunk=chunk, fp8=fp8, synth_chunk=synth_chunk, **export_kwargs):
         if out is None:
             out = np.empty((noise.shape[0],) + a.shape[1:], dtype=np.uint8)

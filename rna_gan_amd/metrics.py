@@ -11,6 +11,9 @@ the device, an evaluation moves F + F^2 doubles per image set to the host and co
 (rg_polykernel_tile_sums), one double per 64 x 64 tile of row pairs to the host and no matrix function at all.
 ``PrecisionRecall`` separates what those two distances mix -- fidelity (precision, density) and diversity (recall, coverage) --
 by k-nearest-neighbour balls in the same feature space (rna_gan_amd.prdc: rg_knn_radii2, rg_radius_hits); four numbers come back.
+``TissueYield`` judges the generated TILES, not features, and needs no real set: the fraction that the reference tiler's acceptance
+rule (rna_gan_amd.tissue: tissue mask coverage and contrast, rg_tile_qc) would keep -- the cheap signal for "the generator emits
+background".
 """
 from __future__ import annotations
 
@@ -301,3 +304,95 @@ class PrecisionRecall(_GeneratedAgainstReal):
         self.last = self.calculate_score(fake, real, radii)
         self.history.append(dict(self.last))
         return float(self.last[self.report])
+
+
+class TissueYield(EvaluationMetric):
+    """The fraction of generated tiles that the reference tiler's acceptance rule keeps (rna_gan_amd.tissue.accept: the dilated
+    tissue mask covers more than ``min_tissue`` of the tile and the tile is not low-contrast) -- the rule every real training tile
+    passed and no generated tile is otherwise held to.  No real set and no feature extractor: ``samples`` generated images go
+    through ``synthesize`` -> ``export.tiles_u8`` (the bytes a tile store would hold) -> ``tissue.tile_stats`` on the device; twelve
+    integers per tile reach the host.
+
+    noise, seed, batch_size, encoding_dims: as FrechetDistance -- (samples, E) standard normal values drawn once from a private
+    torch.Generator(seed), a tensor, or a callable noise(n); the global generators are never touched, the generator runs in eval
+    mode under no_grad and its mode is restored.  rgb_min, dilate, percentiles: of ``tile_stats``; fraction, luma_range: of
+    ``low_contrast``.
+    ``metric_ops`` returns the accepted fraction (what the trainer logs).  ``self.last`` and, per evaluation, ``self.history`` keep
+    {"accepted", "tissue_fraction" (the mean over the tiles), "low_contrast" (the fraction of low-contrast tiles)}; the
+    TileStats of the last evaluation is ``self.last_stats``.  Pickling keeps the settings and ``history``, never the noise."""
+
+    def __init__(self, samples, min_tissue=0.2, rgb_min=50, dilate=3, percentiles=(1, 99), fraction=0.05, luma_range=2.0,
+                 noise=None, seed=0, batch_size=256, encoding_dims=None):
+        super().__init__()
+        self.n_fake = int(samples)
+        if self.n_fake < 1:
+            raise ValueError("samples must be >= 1")
+        self.min_tissue, self.fraction, self.luma_range = float(min_tissue), float(fraction), float(luma_range)
+        self.rgb_min, self.dilate, self.percentiles = int(rgb_min), int(dilate), tuple(float(q) for q in percentiles)
+        from .tissue import MAX_DILATE, percentile_ranks
+        if not 0 <= self.rgb_min <= 255 or not 0 <= self.dilate <= MAX_DILATE:
+            raise ValueError("rgb_min must be in 0..255 and dilate in 0..%d" % MAX_DILATE)
+        percentile_ranks(2, self.percentiles)                    # two percentiles in [0, 100]
+        self.seed = int(seed)
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self._rng = torch.Generator().manual_seed(self.seed)
+        if torch.is_tensor(noise) and noise.shape[0] != self.n_fake:
+            raise ValueError("noise has %d rows, samples is %d" % (noise.shape[0], self.n_fake))
+        self.noise = noise
+        if noise is None and encoding_dims is not None:
+            self.noise = torch.randn(self.n_fake, int(encoding_dims), generator=self._rng)
+        self.last, self.last_stats, self.history = None, None, []
+
+    _noise_for = _GeneratedAgainstReal._noise_for
+    _fake_batches = _GeneratedAgainstReal._fake_batches
+
+    def __getstate__(self):
+        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
+                "min_tissue": self.min_tissue, "fraction": self.fraction, "luma_range": self.luma_range, "rgb_min": self.rgb_min,
+                "dilate": self.dilate, "percentiles": self.percentiles, "history": [dict(h) for h in self.history]}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.noise = None
+        self.last, self.last_stats = None, None
+        self.history = [dict(h) for h in state.get("history", [])]
+        self._rng = torch.Generator().manual_seed(self.seed)
+
+    def preprocess(self, x):
+        """fp32 [-1, 1] NCHW images -> the uint8 tiles a store would hold (interleaved RGB, the rounding rule), on the device."""
+        from .export import tiles_u8
+        return tiles_u8(x.float().contiguous())
+
+    def calculate_score(self, stats):
+        from . import tissue as TQ
+        n = max(len(stats), 1)
+        return {"accepted": float(TQ.accept(stats, self.min_tissue, self.fraction, self.luma_range).sum()) / n,
+                "tissue_fraction": float(TQ.tissue_fraction(stats).sum()) / n,
+                "low_contrast": float(TQ.low_contrast(stats, self.fraction, self.luma_range).sum()) / n}
+
+    @torch.no_grad()
+    def generated_tiles(self, generator, device):
+        """The evaluation's uint8 tiles, one device tensor per batch (eval mode, the mode restored)."""
+        was = generator.training
+        try:
+            generator.eval()
+            z = self._noise_for(generator, device)
+            return [self.preprocess(img) for img in self._fake_batches(generator, z)]
+        finally:
+            generator.train(was)
+
+    def metric_ops(self, generator, device):
+        import numpy as np
+        from . import tissue as TQ
+        rows, H, W = [], 1, 1
+        for tiles in self.generated_tiles(generator, device):
+            H, W = int(tiles.shape[1]), int(tiles.shape[2])
+            rows.append(TQ.tile_stats_device(tiles, rgb_min=self.rgb_min, dilate=self.dilate, percentiles=self.percentiles)[0])
+        stats = TQ.stats_from_rows(torch.cat(rows).cpu().numpy() if rows else np.zeros((0, 12), np.int32), H, W, self.rgb_min,
+                                   self.dilate, self.percentiles)                       # ONE download: 48 bytes per tile
+        self.last_stats = stats
+        self.last = self.calculate_score(stats)
+        self.history.append(dict(self.last))
+        return float(self.last["accepted"])
