@@ -886,6 +886,45 @@ size_t rg_tile_qc_workspace_bytes(int N, int H, int W);
 int rg_tile_qc(const uint8_t* tiles, int N, int H, int W, int flags, int rgb_min, int dilate, const int* ranks4, int32_t* stats,
                uint8_t* mask_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The tiler's device half (rna_gan_amd.tiler; rna_gan_amd/csrc/rg_tiler.hip): windows of a slide raster cropped and resized as
+ * Pillow's 8-bit Image.resize does (bicubic with antialiasing), the erosion that closes a tissue mask, a box thumbnail.  Integer
+ * arithmetic only, so every byte is exact.  Each is ONE plain kernel launch on `stream`: no host synchronisation, no allocation,
+ * no workspace, safe under graph capture.  No 16-bit type is involved: both builds behave identically.
+ *
+ * rg_window_resize_u8
+ *   raster   uint8 [RH][RW][3], interleaved, any alignment.  A pixel outside [0, RH) x [0, RW) reads as 0.  Byte offsets into it
+ *            are 64-bit: RH RW 3 may exceed 2^32.
+ *   origins  DEVICE int32 [N][2]: (x, y) of each window's top-left pixel, x the column; any values, negative or outside included.
+ *   h, w     the read size of every window;  oh, ow  the output size;  out  uint8 [N][oh][ow][3], must not overlap the raster.
+ *   flags    0, or RG_EXPORT_REVERSE: out holds B, G, R (the order of the tile records).
+ *   xtab     DEVICE int32 [ow][2 + kx], ytab DEVICE int32 [oh][2 + ky]: per output index a row (xmin, count, k_0 .. k_{K-1}), zero
+ *            padded -- Pillow's precompute_coeffs + normalize_coeffs_8bpc, made on the HOST in fp64 (rna_gan_amd.tiler.pillow_tables):
+ *              scale = in / out; fs = max(scale, 1); support = 2.0 * fs; K >= (int)ceil(support) * 2 + 1
+ *              center = (i + 0.5) * scale; xmin = max(0, (int)(center - support + 0.5)); xmax = min(in, (int)(center + support + 0.5))
+ *              w_j = bicubic((j + xmin - center + 0.5) / fs), a = -0.5, j < count = xmax - xmin; summed left to right, each divided
+ *              by the sum; k_j = (int)(w_j * 2^22 + 0.5) for w_j >= 0, (int)(w_j * 2^22 - 0.5) otherwise (both truncate toward zero)
+ *   passes   horizontal first: per source row, output column and channel  t = clip(((1 << 21) + sum_j p[xmin + j] k_j) >> 22, 0, 255)
+ *            (arithmetic shift), STORED AS A BYTE; then vertical, the same formula over those bytes with ytab.  The intermediate
+ *            rounding is part of the contract.
+ *   copy     w == ow: the columns are copied and xtab is not read (it may be NULL); h == oh likewise; both: a plain crop.
+ *   RG_EINVAL (nothing launched): a NULL raster / origins / out, N < 0, a size <= 0, an unknown flag bit, misaligned origins or
+ *   tables, a resized axis whose table is NULL or narrower than its K or wider than 35, out overlapping the raster.
+ *   RG_EUNSUPPORTED: oh or ow > 1024, h or w > 8192, an axis that needs K > 35 (a scale above 8.5), more than 2^31 - 1 workgroups.
+ *   N == 0: RG_OK, nothing launched.  A table that is not the contract's gives other bytes, never an access outside the raster or out.
+ *
+ * rg_mask_erode   mask, out: uint8 [N][H][W]; a byte != 0 is set.  out = 1 where every pixel within L1 distance `radius` (0..8) is
+ *   set, everything outside the H x W rectangle counting as UNSET, else 0: scipy's binary_erosion(iterations = radius).  radius 0
+ *   copies (as 0 / 1).  rg_tile_qc's dilated mask followed by this is the binary closing of the reference's thumbnail mask.
+ *   RG_EINVAL: NULL buffer, N < 0, H or W <= 0, radius outside 0..8, out overlapping mask.  RG_EUNSUPPORTED: > 2^31 - 1 workgroups.
+ *
+ * rg_box_reduce_u8   raster uint8 [RH][RW][3] -> out uint8 [ceil(RH / f)][ceil(RW / f)][3]: per channel (sum + cnt / 2) / cnt over
+ *   the f x f block, integer division, cnt the number of the block's pixels inside the raster.  RG_EINVAL: NULL buffer, RH or
+ *   RW <= 0, f outside 1..64, out overlapping the raster. */
+int rg_window_resize_u8(const uint8_t* raster, int RH, int RW, const int32_t* origins, int N, int h, int w, int oh, int ow,
+                        const int32_t* xtab, int kx, const int32_t* ytab, int ky, uint8_t* out, int flags, void* stream);
+int rg_mask_erode(const uint8_t* mask, uint8_t* out, int N, int H, int W, int radius, void* stream);
+int rg_box_reduce_u8(const uint8_t* raster, int RH, int RW, int factor, uint8_t* out, void* stream);
+
 /* ---- the fp32 mode on the bf16 matrix cores, operands split ONCE PER TENSOR (rna_gan_amd/csrc/rg_conv8f.hip, rg_wgrad8f.hip) ----
  * The reference computes in fp32 (src/betaVAE.py:184,223; the GAN CLI never enables AMP).  An fp32 value is the exact sum of three
  * bf16 numbers v = h + m + l; rg_split_planes writes them as a plane-major buffer planes[3][n] (bf16, n % 8 == 0) in one
@@ -927,6 +966,12 @@ int rg_probe_lds_mfma(int mfma_shape, int blocks, int iters, const void* a, cons
                       void* stream);
 int rg_probe_copy(const void* src, void* dst, size_t nbytes, int variant, int blocks, void* stream);
 int rg_probe_fill_bf16(void* p, size_t n, unsigned seed, void* stream);
+/* The two-launch form of rg_window_resize_u8 (rna_gan_amd/csrc/rg_tiler.hip), kept to be measured against (tools/ab_tiler.py): the
+ * same arguments, refusals and bytes, with the byte intermediate [N][h][ow][3] in `workspace` (N h ow 3 bytes).  Like every probe
+ * it is not bound in the fp16 build's table and no product path calls it. */
+int rg_probe_window_resize_2pass(const uint8_t* raster, int RH, int RW, const int32_t* origins, int N, int h, int w, int oh, int ow,
+                                 const int32_t* xtab, int kx, const int32_t* ytab, int ky, uint8_t* out, int flags, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 
 #ifdef __cplusplus

@@ -148,6 +148,9 @@ PROTOTYPES = {
     "rg_tile_export_u8": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _i, _p]),
     "rg_tile_qc_workspace_bytes": (_z, [_i, _i, _i]),
     "rg_tile_qc": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "rg_window_resize_u8": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p]),
+    "rg_mask_erode": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "rg_box_reduce_u8": (_i, [_p, _i, _i, _i, _p, _p]),
     "rg_conv_up_fp8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _f, _i, _p]),
     "rg_gemm_fp8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _f, _i, _p]),
     "rg_fp8_supported": (_i, [_i, _i, _i, _i]),
@@ -200,10 +203,11 @@ PROTOTYPES = {
     "rg_probe_lds_mfma": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
     "rg_probe_copy": (_i, [_p, _p, _z, _i, _i, _p]),
     "rg_probe_fill_bf16": (_i, [_p, _z, C.c_uint, _p]),
+    "rg_probe_window_resize_2pass": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _z, _p]),
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES when an existing entry
-# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc) keeps the number -- load() refuses a library that lacks it
+# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three) keeps the number -- load() refuses a library that lacks it
 ABI_VERSION = 618
 
 _libs = {}

@@ -13,8 +13,8 @@ saturation into 256 bins over the tile's own range (the threshold can differ by 
 ``luma_range = 2.0``, what ``skimage.exposure.is_low_contrast`` effectively applies to a float grey image.
 
 On a CPU tensor ``tile_stats`` computes the same integers with numpy (callers stay testable anywhere); on a CUDA tensor there is no
-fallback: the kernels run or the call raises.  Out of scope: a slide reader, and the slide-level closing (dilate, then erode) of
-the reference's thumbnail mask.
+fallback: the kernels run or the call raises.  The slide-level closing (dilate, then erode) of the reference's thumbnail mask and the
+tiler that applies this rule to a slide raster are rna_gan_amd.tiler; out of scope remains a reader for scanner formats.
 """
 from __future__ import annotations
 
