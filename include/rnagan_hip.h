@@ -219,6 +219,8 @@ int rg_last_up_pre_supported(int Wo, int O, int I, int dtype);
 int rg_last_up_pre(const void* z, const float* w, const float* bias, float* y_nchw, const float* mean, const float* invstd,
                    const float* gamma, const float* beta, float slope, int N, int Ho, int Wo, int O, int I, int apply_tanh,
                    int dtype, void* stream);
+/* rg_skinny_wgrad / rg_skinny_wgrad_bias take a workspace of at least rg_skinny_wgrad_workspace_bytes (RG_EWORKSPACE, nothing
+ * launched, with one byte less -- whichever kernel the shape takes). */
 size_t rg_skinny_wgrad_workspace_bytes(int N, int Ho, int Wo, int O, int I);
 int rg_skinny_wgrad(const void* low, const float* high_nchw, float* dw, int N, int Ho, int Wo, int O, int I,
                     int dtype, int accumulate, void* ws, size_t ws_bytes, void* stream);

@@ -340,6 +340,10 @@ extern "C" int rg_skinny_wgrad(const void* low, const float* high_nchw, float* d
                                int dtype, int accumulate, void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(low && high_nchw && dw && N > 0 && Ho > 0 && Wo > 0 && I > 0 && O > 0, RG_EINVAL,
              "skinny_wgrad: bad args");
+  // the workspace is what the query says, whichever kernel the launch takes (the kernels themselves need less for most shapes:
+  // a caller that sizes the buffer by anything but the query is refused here, not for the one shape that needs all of it)
+  RG_REQUIRE(ws_bytes >= rg_skinny_wgrad_workspace_bytes(N, Ho, Wo, O, I) && (ws || ws_bytes == 0), RG_EWORKSPACE,
+             "skinny_wgrad: workspace smaller than rg_skinny_wgrad_workspace_bytes");
   if (rg_skinny_supported(I, O) && !(dtype == RG_F32 && rg_generic_f32_image_side(N, 2 * Ho, 2 * Wo, I, O)))
     return rg_skinny_wgrad_impl(low, high_nchw, dw, N, Ho, Wo, O, I, dtype, accumulate, ws, ws_bytes,
                                 rg_stream(stream));
@@ -357,6 +361,8 @@ extern "C" int rg_skinny_wgrad_bias(const void* low, const float* high_nchw, flo
   RG_REQUIRE(low && high_nchw && dw && bias_done_out && N > 0 && Ho > 0 && Wo > 0 && I > 0 && O > 0, RG_EINVAL,
              "skinny_wgrad_bias: bad args");
   *bias_done_out = 0;
+  RG_REQUIRE(ws_bytes >= rg_skinny_wgrad_workspace_bytes(N, Ho, Wo, O, I) && (ws || ws_bytes == 0), RG_EWORKSPACE,
+             "skinny_wgrad_bias: workspace smaller than rg_skinny_wgrad_workspace_bytes");
   if (rg_skinny_supported(I, O) && !(dtype == RG_F32 && rg_generic_f32_image_side(N, 2 * Ho, 2 * Wo, I, O)))
     return rg_skinny_wgrad_impl(low, high_nchw, dw, N, Ho, Wo, O, I, dtype, accumulate, ws, ws_bytes, rg_stream(stream),
                                 O == 64 ? dbias : nullptr, bias_accumulate, bias_done_out);
