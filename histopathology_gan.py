@@ -11,7 +11,8 @@ through rna_gan_amd.data (the reference's tile-record format, per-slide sampling
 preparation; slide databases as LMDB files when the ``lmdb`` package is installed, or as directory stores);
 ``--synthetic`` trains on synthetic tiles / RNA rows of the right shapes (what bench.py measures).  Extra flags: --batch_size (reference hard-codes 8),
 --precision, --betavae_checkpoint, --steps_per_epoch; --device_transform 1 hands the uint8 tiles to the device and normalises
-them there, --augment d4 applies one of the eight symmetries of the square per real sample (rna_gan_amd.augment).
+them there, --augment d4 applies one of the eight symmetries of the square per real sample (rna_gan_amd.augment);
+--resident 1 keeps the rank's training tiles on the device as uint8 and forms every batch there (rna_gan_amd.resident).
 """
 import argparse
 import datetime
@@ -109,6 +110,12 @@ EXTRA_FLAGS = [
     ("--augment", str, "none", "none, or d4: every real sample of a training batch is mapped by one of the eight symmetries of "
                                "the square (four rotations, each with or without a flip) drawn per sample from --seed, the rank "
                                "and the batch counter, in the same launch; works on the float batch under --device_transform 0"),
+    ("--resident", int, 0, "1 = the training set is decoded once and kept on the device as uint8 (rna_gan_amd.resident): every "
+                           "batch is gathered, normalised and -- under --augment d4 -- transformed there by one launch, without "
+                           "loader workers or a per-batch host-to-device copy; implies the uint8 datasets; unreadable records "
+                           "are dropped once, every batch is full; the set must fit the device (--resident_max_gb)"),
+    ("--resident_max_gb", float, 0.0, "--resident 1: the memory budget of the set in GiB (0 = the device's free memory minus "
+                                      "8 GiB); a set that needs more is refused before anything is uploaded"),
 ]
 
 
@@ -169,6 +176,10 @@ def parse_args(argv=None):
         ap.error("--device_transform must be 0 or 1")
     if args.augment not in ("none", "d4"):
         ap.error("--augment must be none or d4")
+    if args.resident not in (0, 1):
+        ap.error("--resident must be 0 or 1")
+    if args.resident_max_gb < 0:
+        ap.error("--resident_max_gb must be >= 0")
     return args
 
 
@@ -284,13 +295,15 @@ def main():
     rna_features = config.get("rna_features", 19198)
     with_rna = args.loss_type == "wganvae"
     input_transform = None
-    if args.device_transform or args.augment != "none":
+    if args.device_transform or args.augment != "none" or args.resident:
         from rna_gan_amd.augment import InputTransform
         input_transform = InputTransform(0.5, 0.5, augment=args.augment, seed=args.seed, rank=D_.rank())
     if args.synthetic:
         ds = SyntheticTiles(args.steps_per_epoch * args.batch_size, img_size, rna_features, with_rna,
-                            args.seed + 1000 * D_.rank(), as_u8=bool(args.device_transform))
-        loader = DataLoader(ds, batch_size=args.batch_size, num_workers=0, pin_memory=True, drop_last=True)
+                            args.seed + 1000 * D_.rank(), as_u8=bool(args.device_transform or args.resident))
+        shard = None                                       # (every rank draws a set of its own: the whole of it is its shard)
+        if not args.resident:
+            loader = DataLoader(ds, batch_size=args.batch_size, num_workers=0, pin_memory=True, drop_last=True)
     else:
         # the reference's data path (src/histopathology_gan.py:111-168): slide tables -> [log + StandardScaler on the
         # rna_ columns] -> per-slide tile sampling from the slide databases -> batches; rna_gan_amd.data restates the
@@ -302,7 +315,8 @@ def main():
         random.seed(args.seed)
         patch_data_path = config["patch_data_path"]
         train_df = PD.load_slide_tables(config["path_csv"], patch_data_path)
-        tf = None if args.device_transform else PD.ToFloatNormalize(0.5, 0.5)   # None: uint8 tiles, normalised on the device
+        # None: uint8 tiles, normalised on the device
+        tf = None if args.device_transform or args.resident else PD.ToFloatNormalize(0.5, 0.5)
         if with_rna:
             train_df, _, _ = PD.log_standardize_rna(train_df)
             ds = PD.PatchRNADataset(patch_data_path, train_df, img_size, max_patches_total=args.num_patches, transforms=tf)
@@ -311,12 +325,14 @@ def main():
 
         world = D_.world_size()
         collate_fn = make_collate_fn(with_rna, world)
-        if world > 1:
-            # one shard of the (identical) tile list per rank, the SAME number of full batches on every rank: each train_op
-            # issues a gradient all-reduce, so a rank with one batch more would pair its collectives with nobody
-            ds = torch.utils.data.Subset(ds, shard_indices(len(ds), D_.rank(), world, args.batch_size))
-        loader = DataLoader(ds, batch_size=args.batch_size, num_workers=4, pin_memory=True, collate_fn=collate_fn,
-                            drop_last=world > 1)   # :163-168
+        shard = shard_indices(len(ds), D_.rank(), world, args.batch_size) if world > 1 else None
+        if not args.resident:
+            if world > 1:
+                # one shard of the (identical) tile list per rank, the SAME number of full batches on every rank: each train_op
+                # issues a gradient all-reduce, so a rank with one batch more would pair its collectives with nobody
+                ds = torch.utils.data.Subset(ds, shard)
+            loader = DataLoader(ds, batch_size=args.batch_size, num_workers=4, pin_memory=True, collate_fn=collate_fn,
+                                drop_last=world > 1)   # :163-168
 
     if args.gan_type not in ("dcgan", "dcgan_up"):
         raise SystemExit("--gan_type dcgan (the reference CLI's path) or dcgan_up (src/dcgan.py's DCGANUpGenerator, "
@@ -365,8 +381,19 @@ def main():
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,
                         ema_decay=args.g_ema if args.g_ema > 0.0 else None, ema_warmup=bool(args.g_ema_warmup),
-                        input_transform=input_transform)
+                        input_transform=None if args.resident else input_transform)   # resident: the loader's transform
     holder["trainer"] = trainer
+    if args.resident:
+        # the rank's shard, read once and kept on the device; the evaluation sets above keep their own path (the first N items
+        # of ds, normalised by the same transform without a draw)
+        from rna_gan_amd.resident import DeviceTileLoader, DeviceTileSet
+        tiles = DeviceTileSet.from_dataset(ds, device, items=shard, workers=0 if args.synthetic else 4,
+                                           max_bytes=int(args.resident_max_gb * (1 << 30)) if args.resident_max_gb > 0 else None)
+        print("Resident set on {}: {} tiles, {} bytes, {} unreadable records dropped, built in {:.1f} s".format(
+            device, len(tiles), tiles.nbytes, tiles.dropped, tiles.build_seconds))
+        loader = DeviceTileLoader(tiles, args.batch_size, transform=input_transform, seed=args.seed, rank=D_.rank())
+        if len(loader) == 0:
+            raise SystemExit("--resident 1: %d readable tiles do not fill one batch of %d" % (len(tiles), args.batch_size))
     if args.checkpoint is not None:
         trainer.load_model(load_path=args.checkpoint)
     for loss in losses:                                   # identical frozen encoders on every rank (rank 0's)

@@ -832,7 +832,24 @@ int rg_u8_to_norm(const void* src_u8, float* dst, size_t n, float mean, float st
 int rg_tile_transform(const void* src, int src_dtype, float* dst, int N, int C, int S, const int* codes, float mean, float stdv,
                       void* stream);
 
-/* The device-side tile export (rna_gan_amd.export; rna_gan_amd/csrc/rg_export.hip): generated images -> uint8 tiles, quantised and
+/* The batch of a RESIDENT training set (rna_gan_amd.resident; rna_gan_amd/csrc/rg_augment.hip): gather, normalise and D4 in one
+ * launch -- rg_tile_transform with a per-sample source tile.
+ *   store [M][C][S][S] uint8, the whole set on the device;  dst [N][C][S][S] fp32
+ *   index device array of N ints, or NULL = index[n] = n (then N <= M is required, and the output is bit-identical to
+ *         rg_tile_transform(store, RG_U8, ...) on the first N tiles).  Repeated indices are allowed.
+ *   dst[n] = the rg_tile_transform result for tile store[index[n]] under code codes[n] & 7 (codes NULL = 0): the same three
+ *         separately rounded fp32 operations, the same code table.
+ * Every source offset is computed in 64 bits.  The kernel never reads outside store[0 .. M): an index outside [0, M) is CLAMPED
+ * to the nearest valid tile (negative -> 0, >= M -> M - 1).  That is a memory-safety guarantee, not an interface: callers
+ * validate their indices.  No workspace; nothing outside dst is written; store and dst must not overlap; S % 4 == 0 with a
+ * 4-byte-aligned store and a 16-byte-aligned dst takes the vector path for every gathered tile (C S S is then a multiple of 4),
+ * same bits.  No host synchronisation, no allocation, safe under graph capture, any stream.  N == 0: RG_OK, nothing launched.
+ * RG_EINVAL (nothing launched) for a NULL store or dst, M <= 0 with N > 0, N < 0, C <= 0, S <= 0, stdv == 0, or index == NULL
+ * with N > M; RG_EUNSUPPORTED for more than 2^31 - 1 tiles of 64 x 64.  Both builds behave identically. */
+int rg_tile_gather_transform(const uint8_t* store, long long M, const int* index, float* dst, int N, int C, int S,
+                             const int* codes, float mean, float stdv, void* stream);
+
+/* The device-side tile export(rna_gan_amd.export; rna_gan_amd/csrc/rg_export.hip): generated images -> uint8 tiles, quantised and
  * laid out in one launch, so a batch leaves the device as C bytes per pixel instead of 4 C.
  *   src   [N][C][H][W] fp32;  dst N C H W bytes
  *   flags RG_EXPORT_PLANAR   clear: dst [N][H][W][C], interleaved (a PNG, a tile record);  set: dst [N][C][H][W]

@@ -10,7 +10,8 @@ from .optim import Adam  # noqa: F401
 from .ema import ParamEMA  # noqa: F401
 from .metrics import EvaluationMetric, FrechetDistance, KernelDistance, PrecisionRecall  # noqa: F401
 from .augment import InputTransform  # noqa: F401
+from .resident import DeviceTileLoader, DeviceTileSet  # noqa: F401
 
-__all__ = ["InputTransform","DCGANGenerator", "DCGANUpGenerator", "DCGANDiscriminator", "Generator", "Discriminator", "betaVAE", "Trainer", "Adam", "ParamEMA", "EvaluationMetric", "FrechetDistance", "KernelDistance", "PrecisionRecall",
+__all__ = ["InputTransform", "DeviceTileSet", "DeviceTileLoader", "DCGANGenerator", "DCGANUpGenerator", "DCGANDiscriminator", "Generator", "Discriminator", "betaVAE", "Trainer", "Adam", "ParamEMA", "EvaluationMetric", "FrechetDistance", "KernelDistance", "PrecisionRecall",
            "WassersteinGeneratorLoss", "WassersteinDiscriminatorLoss", "WassersteinGradientPenalty",
            "WassersteinGeneratorLossVAE", "WassersteinDiscriminatorLossVAE", "WassersteinGradientPenaltyVAE"]

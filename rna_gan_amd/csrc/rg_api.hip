@@ -18,7 +18,7 @@ void rg_set_error(const char* fmt, ...) {
 }
 
 // bumped whenever an entry point is added or a signature changes; rna_gan_amd/_abi.py (ABI_VERSION) refuses any other value
-extern "C" int rg_version(void) { return 618; }   // 6.18: rg_knn_radii2 / rg_radius_hits / rg_pairdist_ws_bytes (rg_knn.hip: precision, recall, density, coverage); rg_tile_transform (rg_augment.hip), rg_tile_export_u8 (rg_export.hip) and rg_tile_qc (rg_tissue.hip) were added without a new number: no existing entry point changed
+extern "C" int rg_version(void) { return 618; }   // 6.18: rg_knn_radii2 / rg_radius_hits / rg_pairdist_ws_bytes (rg_knn.hip: precision, recall, density, coverage); rg_tile_transform and rg_tile_gather_transform (rg_augment.hip), rg_tile_export_u8 (rg_export.hip) and rg_tile_qc (rg_tissue.hip) were added without a new number: no existing entry point changed
 extern "C" const char* rg_last_error(void) { return g_err; }
 
 // ---- kernel-selection knobs: override table in front of the RNAGAN_* environment variables

@@ -8,6 +8,8 @@
 // steps, so the transposing codes (1, 3, 5, 7) never read global memory with a stride of S.  The LDS pitch is 65 dwords: a
 // column walk (address step 65) visits bank (l + c) % 32 for lane l, conflict-free like a row walk.  No 16-bit type is
 // involved: both builds of the library behave identically.
+// rg_tile_gather_transform is the same kernel with a per-sample SOURCE tile: the batches of a training set that lives on the
+// device as uint8 (rna_gan_amd.resident) are gathered by index, normalised and transformed in that one launch.
 #include "rg_common.h"
 
 namespace {
@@ -42,9 +44,13 @@ template <> struct TileSrc<float> {
 //   src  [i][j] [j][T-i] [T-i][T-j] [T-j][i] [i][T-j] [j][i]  [T-i][j] [T-j][T-i]
 // VEC: S % 4 == 0 and both buffers aligned to four elements -- every tile origin, tile width and plane offset is then a multiple
 // of 4, and the tile is fetched and stored four elements per lane.
-template <typename SrcT, bool VEC>
+// GATHER (rg_tile_gather_transform): sample n reads tile index[n] (NULL: n) of a store of M tiles instead of tile n of the batch.
+// The index is read once per workgroup, next to the code, clamped into [0, M) and widened before the multiplication; nothing
+// else differs, and without GATHER the two extra arguments are never looked at.
+template <typename SrcT, bool VEC, bool GATHER>
 __global__ __launch_bounds__(256) void tile_transform_kernel(const SrcT* __restrict__ src, float* __restrict__ dst, int C, int S,
-                                                             int tiles, const int* __restrict__ codes, float mean, float stdv) {
+                                                             int tiles, const int* __restrict__ codes, float mean, float stdv,
+                                                             const int* __restrict__ index, long long M) {
   __shared__ float lds[TT_TILE * TT_PITCH];
   const int tid = threadIdx.x;
   const int per_plane = tiles * tiles;
@@ -61,7 +67,14 @@ __global__ __launch_bounds__(256) void tile_transform_kernel(const SrcT* __restr
   const int r0 = rflip ? S - u0 - nu : u0;
   const int c0 = cflip ? S - v0 - nv : v0;
   const size_t base = (size_t)plane * S * S;
-  const SrcT* sp = src + base;
+  size_t sbase = base;
+  if (GATHER) {
+    const int n = plane / C;
+    long long t = index ? (long long)index[n] : (long long)n;    // uniform: one sample, one source tile
+    t = t < 0 ? 0 : (t >= M ? M - 1 : t);                        // a bad index reads a valid tile, never outside the store
+    sbase = ((size_t)t * C + (size_t)(plane - n * C)) * S * S;   // 64-bit throughout: t C S S passes 2^32 in a resident set
+  }
+  const SrcT* sp = src + sbase;
   float* dp = dst + base;
 
   // ---- fetch: coalesced rows of the source tile, converted at the LDS store
@@ -132,11 +145,11 @@ void launch_tile_transform(const void* src, float* dst, int C, int S, int tiles,
   // four elements of either buffer per access: S % 4 == 0 keeps every row, tile and plane a multiple of 4 from the base
   const bool vec = S % 4 == 0 && ((uintptr_t)src & (4 * sizeof(SrcT) - 1)) == 0 && ((uintptr_t)dst & 15) == 0;
   if (vec)
-    hipLaunchKernelGGL((tile_transform_kernel<SrcT, true>), dim3(blocks), dim3(256), 0, st, (const SrcT*)src, dst, C, S, tiles,
-                       codes, mean, stdv);
+    hipLaunchKernelGGL((tile_transform_kernel<SrcT, true, false>), dim3(blocks), dim3(256), 0, st, (const SrcT*)src, dst, C, S,
+                       tiles, codes, mean, stdv, (const int*)nullptr, 0LL);
   else
-    hipLaunchKernelGGL((tile_transform_kernel<SrcT, false>), dim3(blocks), dim3(256), 0, st, (const SrcT*)src, dst, C, S, tiles,
-                       codes, mean, stdv);
+    hipLaunchKernelGGL((tile_transform_kernel<SrcT, false, false>), dim3(blocks), dim3(256), 0, st, (const SrcT*)src, dst, C, S,
+                       tiles, codes, mean, stdv, (const int*)nullptr, 0LL);
 }
 
 }  // namespace
@@ -157,5 +170,30 @@ extern "C" int rg_tile_transform(const void* src, int src_dtype, float* dst, int
   else
     launch_tile_transform<float>(src, dst, C, S, tiles, (unsigned)blocks, codes, mean, stdv, rg_stream(stream));
   RG_LAUNCH_CHECK("tile_transform");
+  return RG_OK;
+}
+
+// The resident training set (rna_gan_amd.resident): the same launch plan with a per-sample source tile.  S % 4 == 0 makes C S S
+// a multiple of 4, so every gathered tile is as aligned as the store's base and one test chooses the path for all of them.
+extern "C" int rg_tile_gather_transform(const uint8_t* store, long long M, const int* index, float* dst, int N, int C, int S,
+                                        const int* codes, float mean, float stdv, void* stream) {
+  RG_REQUIRE(store && dst, RG_EINVAL, "tile_gather_transform: NULL buffer");
+  RG_REQUIRE(N >= 0 && C > 0 && S > 0, RG_EINVAL, "tile_gather_transform: bad shape N %d C %d S %d", N, C, S);
+  RG_REQUIRE(M > 0 || N == 0, RG_EINVAL, "tile_gather_transform: a store of %lld tiles cannot fill %d samples", M, N);
+  RG_REQUIRE(stdv != 0.f, RG_EINVAL, "tile_gather_transform: std must not be 0");
+  RG_REQUIRE(index || (long long)N <= M, RG_EINVAL, "tile_gather_transform: no index and N %d > M %lld", N, M);
+  if (N == 0) return RG_OK;
+  const int tiles = (S + TT_TILE - 1) / TT_TILE;
+  const long long blocks = (long long)N * C * tiles * tiles;
+  RG_REQUIRE(blocks <= 0x7fffffffLL, RG_EUNSUPPORTED, "tile_gather_transform: more than 2^31 - 1 tiles");
+  const bool vec = S % 4 == 0 && ((uintptr_t)store & 3) == 0 && ((uintptr_t)dst & 15) == 0;
+  hipStream_t st = rg_stream(stream);
+  if (vec)
+    hipLaunchKernelGGL((tile_transform_kernel<uint8_t, true, true>), dim3((unsigned)blocks), dim3(256), 0, st, store, dst, C, S,
+                       tiles, codes, mean, stdv, index, M);
+  else
+    hipLaunchKernelGGL((tile_transform_kernel<uint8_t, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, store, dst, C, S,
+                       tiles, codes, mean, stdv, index, M);
+  RG_LAUNCH_CHECK("tile_gather_transform");
   return RG_OK;
 }

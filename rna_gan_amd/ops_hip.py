@@ -798,6 +798,30 @@ class HipOps:
                                          _ptr(codes), float(mean), float(std), self.stream), "rg_tile_transform")
         return y
 
+    def tile_gather_transform(self, store, index=None, codes=None, n=None, mean=0.5, std=0.5):
+        """One batch of a resident set (rg_tile_gather_transform): sample k is tile ``store[index[k]]`` of the uint8 device store
+        [M][C][S][S], normalised as u8_to_norm and mapped by ``codes[k] & 7``.  index: int32 device tensor (None = the first
+        ``n`` tiles); codes: int32 device tensor of as many entries (None = the identity).  The caller validates the indices:
+        the kernel clamps a bad one into the store, which is memory safety and not an interface.  One launch."""
+        assert store.dim() == 4 and store.shape[2] == store.shape[3] and store.is_contiguous() and store.is_cuda
+        assert store.dtype == torch.uint8
+        M, C, S, _ = store.shape
+        if index is not None:
+            assert index.dtype == torch.int32 and index.is_cuda and index.is_contiguous() and index.dim() == 1
+            N = index.numel() if n is None else int(n)
+            assert N <= index.numel()
+        else:
+            N = M if n is None else int(n)
+            assert N <= M
+        if codes is not None:
+            assert codes.dtype == torch.int32 and codes.is_cuda and codes.is_contiguous() and codes.numel() >= N
+        y = self._f32(N, C, S, S)
+        if N == 0:
+            return y
+        check(self.lib.rg_tile_gather_transform(_ptr(store), M, _ptr(index), _ptr(y), N, C, S, _ptr(codes), float(mean),
+                                                float(std), self.stream), "rg_tile_gather_transform")
+        return y
+
     def export_images_nhwc(self, img_nchw):
         """NCHW fp32 in [-1,1] -> NHWC fp32 in [0,1] (un-normalise + permute, src/gan_utils.py:236-241)."""
         N, C, H, W = img_nchw.shape

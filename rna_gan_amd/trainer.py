@@ -46,6 +46,10 @@ class Trainer:
         # in front of train_iter; None (the default) leaves the batch as the loader made it
         self.input_transform = input_transform
         self.prefetch = bool(prefetch)          # extra knob: host batches are copied to the device one iteration ahead
+        # a loader with a state of its own (rna_gan_amd.resident.DeviceTileLoader: the epoch of its order stream): train()
+        # remembers it, save_model writes its state under "data_loader", load_model stashes that entry for train() to apply
+        self._data_loader = None
+        self._data_loader_state = None
         self.pipeline = bool(kwargs.pop("pipeline", True))   # extra knob: see train_iter
         self.model_names = []
         self.optimizer_names = []
@@ -159,6 +163,8 @@ class Trainer:
             model["ema_information"] = {"decay": self.ema.decay, "warmup": self.ema.warmup}
         if self.input_transform is not None:
             model["input_transform"] = self.input_transform.state_dict()
+        if self._data_loader is not None:
+            model["data_loader"] = self._data_loader.state_dict()
         if save_items is not None:
             for it in ([save_items] if isinstance(save_items, str) else save_items):
                 model.update({it: getattr(self, it)})
@@ -207,6 +213,8 @@ class Trainer:
                     print("load_model: the checkpoint holds no averaged generator: the average restarts from the loaded generator")
             if self.input_transform is not None and "input_transform" in checkpoint:   # (ignored when no transform is set)
                 self.input_transform.load_state_dict(checkpoint["input_transform"])
+            if "data_loader" in checkpoint:                # applied by train() to the loader it is given, if that one has a state
+                self._data_loader_state = checkpoint["data_loader"]
             if load_items is not None:
                 for it in ([load_items] if isinstance(load_items, str) else load_items):
                     obj = checkpoint[it]
@@ -402,12 +410,26 @@ class Trainer:
         self._store_metric_maps()
         if self.test_noise is None:
             self.test_noise = self.generator.sampler(self.sample_size, self.device)
+        # a loader of FINAL images (rna_gan_amd.resident.DeviceTileLoader): already on the device and already transformed
+        final = bool(getattr(data_loader, "final_images", False))
+        if final and self.input_transform is not None:
+            raise ValueError("the loader yields final images (its own transform normalised them and applied the D4 symmetry): "
+                             "a Trainer with input_transform set would transform them a second time -- give the transform "
+                             "to the loader alone")
+        stateful = hasattr(data_loader, "state_dict") and hasattr(data_loader, "load_state_dict")
+        self._data_loader = data_loader if stateful else None
+        if stateful and self._data_loader_state is not None:
+            data_loader.load_state_dict(self._data_loader_state)
+        self._data_loader_state = None
+        # (nothing to prefetch from such a loader; and running it one batch ahead would leave its transform's last_codes
+        # one batch ahead of real_inputs)
+        prefetch = self.prefetch and not final
         for epoch in range(self.start_epoch, self.epochs):
             for name in self.model_names:
                 getattr(self, name).train()
             # batches arrive on the device one iteration ahead (rna_gan_amd/prefetch.py); the .to() calls below and the
             # plugins' own then find the tensors in place
-            for data in (DevicePrefetcher(data_loader, self.device) if self.prefetch else data_loader):
+            for data in (DevicePrefetcher(data_loader, self.device) if prefetch else data_loader):
                 if self.input_transform is not None:
                     data = self._transform_batch(data)
                 if isinstance(data, (tuple, list)):
