@@ -64,28 +64,24 @@ extern "C" int rg_pack_conv_weight(const float* w, void* wdn, void* wup, int O, 
   return rg_mfma_pack_conv_weight(w, wdn, wup, O, I, rg_stream(stream));
 }
 
+// ---- what the Python side asks about a conv launch before it sizes its buffers: every answer is a field of the launch's
+// own plan (rg_mfma_conv_plan); a shape or dtype the matrix-core kernels do not take has none
+static bool conv_planned(int up, int N, int Hlow, int Wlow, int O, int I, int dtype, int algo) {
+  return N > 0 && Hlow > 0 && Wlow > 0 && O > 0 && I > 0 && want_mfma(algo, dtype) &&
+         rg_mfma_conv_supported(N, Hlow, Wlow, up ? O : I, up ? I : O);
+}
 extern "C" size_t rg_conv_workspace_bytes(int up, int N, int Hlow, int Wlow, int O, int I, int dtype, int algo) {
-  if (!want_mfma(algo, dtype)) return 0;
-  if (!rg_mfma_conv_supported(N, Hlow, Wlow, up ? O : I, up ? I : O)) return 0;
-  return rg_mfma_conv_ws_bytes(up, N, Hlow, Wlow, O, I);
+  return conv_planned(up, N, Hlow, Wlow, O, I, dtype, algo) ? rg_mfma_conv_plan(up, N, Hlow, Wlow, O, I).ws_bytes : 0;
 }
-
 extern "C" int rg_conv_stats_rows(int up, int N, int Hlow, int Wlow, int O, int I, int dtype, int algo) {
-  if (N <= 0 || Hlow <= 0 || Wlow <= 0 || O <= 0 || I <= 0 || !want_mfma(algo, dtype)) return 0;
-  if (!rg_mfma_conv_supported(N, Hlow, Wlow, up ? O : I, up ? I : O)) return 0;
-  return rg_mfma_conv_stats_rows(up, N, Hlow, Wlow, O, I);
+  return conv_planned(up, N, Hlow, Wlow, O, I, dtype, algo) ? rg_mfma_conv_plan(up, N, Hlow, Wlow, O, I).stats_rows : 0;
 }
-
-// ---- split-K launches whose slab reduction is left to the consumer (rg_bn_forward_slabs / rg_bn_act_bwd_slabs)
+// split-K launches whose slab reduction is left to the consumer (rg_bn_forward_slabs / rg_bn_act_bwd_slabs)
 extern "C" int rg_conv_split(int up, int N, int Hlow, int Wlow, int O, int I, int dtype, int algo) {
-  if (N <= 0 || Hlow <= 0 || Wlow <= 0 || O <= 0 || I <= 0 || !want_mfma(algo, dtype)) return 1;
-  if (!rg_mfma_conv_supported(N, Hlow, Wlow, up ? O : I, up ? I : O)) return 1;
-  return rg_mfma_conv_nsplit(up, N, Hlow, Wlow, O, I);
+  return conv_planned(up, N, Hlow, Wlow, O, I, dtype, algo) ? rg_mfma_conv_plan(up, N, Hlow, Wlow, O, I).nsplit : 1;
 }
-
 extern "C" int rg_conv_slab_dtype(int up, int N, int Hlow, int Wlow, int O, int I, int dtype, int algo) {
-  if (rg_conv_split(up, N, Hlow, Wlow, O, I, dtype, algo) <= 1) return RG_F32;
-  return rg_mfma_conv_slab16(up, N, Hlow, Wlow, O, I) ? RG_H16 : RG_F32;
+  return conv_planned(up, N, Hlow, Wlow, O, I, dtype, algo) && rg_mfma_conv_plan(up, N, Hlow, Wlow, O, I).slab16 ? RG_H16 : RG_F32;
 }
 
 extern "C" int rg_conv_down_partial(const void* x, const void* wdn, int N, int Hi, int Wi, int I, int O, int dtype, int algo,
@@ -137,8 +133,10 @@ extern "C" size_t rg_conv_wgrad_workspace_bytes(int N, int Ho, int Wo, int O, in
   size_t b = 0;
   if (want_mfma(algo, dtype) && rg_mfma_wgrad_supported(N, Ho, Wo, O, I)) {
     b = rg_mfma_wgrad_ws_bytes(N, Ho, Wo, O, I);
-    size_t c = rg_mfma_wgrad2_ws_bytes(N, Ho, Wo, O, I);
-    if (c > b) b = c;
+    for (int two = 0; two < 2; ++two) {       // the caller may hand one segment or two to the launch
+      const size_t c = rg_mfma_wgrad_plan(N * Ho * Wo, two != 0, O, I).ws_bytes;
+      if (c > b) b = c;
+    }
   }
   return a > b ? a : b;
 }
@@ -185,8 +183,9 @@ extern "C" int rg_conv_wgrad_slabs(const void* low0, const void* high0, const vo
 // (bf16 operands, the matrix-core kernel without split-K); the caller's streaming step must leave the tensor out
 // (rg_adam_step_slabs: a segment with nsplit = -1).
 extern "C" int rg_conv_wgrad_adam_supported(int N, int Ho, int Wo, int O, int I, int two, int dtype, int algo) {
-  return N > 0 && Ho > 0 && Wo > 0 && O > 0 && I > 0 && want_mfma(algo, dtype) && rg_mfma_wgrad_supported(N, Ho, Wo, O, I) &&
-         rg_mfma_conv_wgrad_adam_supported(N, Ho, Wo, O, I, two != 0) ? 1 : 0;
+  if (!(N > 0 && Ho > 0 && Wo > 0 && O > 0 && I > 0 && want_mfma(algo, dtype) && rg_mfma_wgrad_supported(N, Ho, Wo, O, I))) return 0;
+  const RgWgradPlan pl = rg_mfma_wgrad_plan(N * Ho * Wo, two != 0, O, I);
+  return pl.kernel == RG_WK_WGRAD8 && pl.nsplit == 1 ? 1 : 0;
 }
 extern "C" int rg_conv_wgrad_adam(const void* low0, const void* high0, const void* low1, const void* high1, float* p, float* m,
                                   float* v, const float* hyper, void* shadow_bf16, int N, int Ho, int Wo, int O, int I, int dtype,

@@ -273,8 +273,6 @@ bool rg_convd_supported(int M, int Ncols, int Cin, int Hs, int Ws) {
   return Ncols == 128 && Cin == 64 && Ws == 128 && Hs >= 8 && rg_is_pow2(Hs) && M % 256 == 0 && M >= 256;
 }
 
-int rg_convd_stats_rows(int M) { return M / 64; }
-
 int rg_convd_launch(const void* args, hipStream_t st) {
   const G2Args& a2 = *reinterpret_cast<const G2Args*>(args);
   const int tiles = a2.g.M / 256;

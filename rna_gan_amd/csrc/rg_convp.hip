@@ -501,8 +501,6 @@ bool rg_convp_supported(int M, int Ncols, int Cin, int Hs, int Ws) {
          M % 256 == 0 && M >= 256;
 }
 
-int rg_convp_tiles(int M) { return M / 256; }
-
 int rg_convp_launch(const void* args, hipStream_t st) {
   const G2Args& a2 = *reinterpret_cast<const G2Args*>(args);
   const int tiles = a2.g.M / 256;

@@ -1238,15 +1238,42 @@ static int launch_gather(const char* name, GArgs& g, int nclass, hipStream_t st)
 }
 
 static bool use_v1() { return rg_option("conv_v1", 0) == 1; }
+// the LDS-DMA kernels address an operand through a buffer descriptor and 32-bit offsets: below 2 GB
+static bool fits_descriptor(size_t bytes) { return bytes < 0x7fffff00ull; }
 
-// split-K policy of the DMA kernel: only when the grid cannot fill the chip (< 1 block per CU) and K is long
-// tile variant / split-K decision of the DMA kernel, shared by the launcher and by rg_mfma_conv_stats_rows
-struct GPlan { bool narrow, wide; int nsplit; bool c8; int bm, bn; bool n8, pp, pd; };
+// ---- the launch plan (RgConvPlan, rg_internal.h).  gather_plan() is the only place that decides kernel, tile and split-K of a
+// gather GEMM; rg_mfma_conv_plan (convs) and gemm_plan (plain GEMMs, linear layers, the 3 x 3 convs) describe their shape to
+// it, the queries of rg_api.hip read the struct, and launch_gather2 switches on it.
+struct GShape {
+  int mode; bool bf16_out;
+  int M, Ncols, Cin, taps, nclass;   // rows per parity class, output columns, channels per tap (k-tiles: taps * Cin / 64)
+  int ld;                            // row length of the output = of a split-K slab
+  int Hs, Ws;                        // spatial dims of the tensor the rows are gathered from
+  size_t a_bytes, b_bytes;
+  bool masked, dense_mask;           // a mask / affine epilogue is fused; that mask is a dense activation (not packed bits)
+};
 
-static int gather_split(int M, int Ncols, int nclass, int nkt, bool allow, int cap = 4, int min_kt = 16) {
-  if (!allow) return 1;
-  int bn = Ncols <= 64 ? 64 : 128, bmm = bn == 128 ? 128 : 256;
-  long long tiles = (long long)((M + bmm - 1) / bmm) * ((Ncols + bn - 1) / bn) * nclass;
+// Tile of each kernel, and the rows that one wave's accumulators span: an epilogue that sums BatchNorm columns writes
+// bm / wave_rows partial rows per tile.
+struct KernelTile { int bm, bn, wave_rows; };
+static KernelTile kernel_tile(RgConvKernel k) {
+  switch (k) {
+    case RG_CK_PATCH: return {256, 64, 128};
+    case RG_CK_PLANES: return {256, 128, 64};
+    case RG_CK_NARROW8: return {512, 64, 64};
+    case RG_CK_C8_256: return {256, 256, 128};
+    case RG_CK_C8_512: return {512, 128, 128};
+    case RG_CK_T256X64: case RG_CK_T256X64_N32: return {256, 64, 64};
+    case RG_CK_T256: return {256, 256, 128};
+    case RG_CK_STREAM64: return {64, 128, 64};
+    default: return {128, 128, 64};      // RG_CK_T128 (and RG_CK_LEGACY: its own 128 x 128 launch)
+  }
+}
+static bool is_conv8(RgConvKernel k) { return k == RG_CK_C8_256 || k == RG_CK_C8_512; }
+
+// split-K policy of the 2-stage kernel on a bm x bn tile: only when the grid cannot fill the chip and K is long
+static int gather_split(int M, int Ncols, int nclass, int nkt, KernelTile t, int cap, int min_kt) {
+  long long tiles = (long long)((M + t.bm - 1) / t.bm) * ((Ncols + t.bn - 1) / t.bn) * nclass;
   // fewer than 2 blocks per CU leaves half of the wave slots empty (1 wave/SIMD cannot hide the LDS/DMA waits)
   if (tiles >= 512 || nkt < 2 * min_kt) return 1;
   int s = (int)((512 + tiles - 1) / tiles);
@@ -1261,7 +1288,7 @@ static int gather_split(int M, int Ncols, int nclass, int nkt, bool allow, int c
 // the tile saves): RNAGAN_CONV_TILE=0 disables it, =5 forces it wherever it fits (with split-K).
 // Split-K: conv outputs up to 4 splits; dense weight-streaming layers (M = batch) up to 16 (HBM-bound, the grid
 // must cover all CUs to pull full bandwidth); none when a mask is fused into the bf16 epilogue.
-// c8: the 8-wave ping-pong kernel of rg_conv8.hip (256x256 or 512x128 tiles) takes the bf16-output conv / plain
+// The 8-wave ping-pong kernel of rg_conv8.hip (256x256 or 512x128 tiles) takes the bf16-output conv / plain
 // GEMMs whose shape it supports (RNAGAN_CONV8=0: off).
 // conv8: 0 off; bit 0 on; bit 2 (default) also where the tile count needs split-K.  With the tap-major k order the split form
 // lost to the 128 x 128 kernel (81-88 vs 68-78 us per deep layer at batch 64); with the channel-block-major order (korder) a
@@ -1270,174 +1297,187 @@ static int gather_split(int M, int Ncols, int nclass, int nkt, bool allow, int c
 static int conv8_mode() { return rg_option("conv8", 5); }
 static int conv8_blocks_target() { return rg_option("conv8_blocks", 256); }
 
-static GPlan gather_plan(int mode, bool bf16_out, int M, int Ncols, int Cin, int taps, int nclass, bool masked, int Hs = 0,
-                         int Ws = 0, bool has_mask = false) {
-  const int variant = rg_option("conv_tile", 1);
-  const int nkt = taps * (Cin >> 6);
-  GPlan pl{};
-  const int cpt = Cin >> 6;
-  // n8: the 64-column transposed conv with all four parity classes per block (conv8n_kernel).  Measured at batch 64
+// The tile table.  lds_resident = false leaves out the two kernels that keep their input in LDS.
+struct Pick { RgConvKernel kernel; int nsplit; };
+static Pick pick_kernel(const GShape& s, bool lds_resident, bool masked) {
+  const int cpt = s.Cin >> 6, nkt = s.taps * cpt, M = s.M, Ncols = s.Ncols;
+  const bool conv_up = s.bf16_out && s.mode == MODE_UP && s.nclass == 4;
+  // the 128 -> 64 channel transposed conv with the input patch resident in LDS (rg_convp.hip; RNAGAN_CONVP=0: off)
+  if (lds_resident && rg_option("convp", RG_CONVP_DEFAULT) && !s.dense_mask && conv_up && s.taps == 4 &&
+      rg_convp_supported(M, Ncols, s.Cin, s.Hs, s.Ws))
+    return {RG_CK_PATCH, 1};
+  // the 64 -> 128 channel stride-2 conv on a 128-pixel-wide input with its parity planes resident in LDS (rg_convd.hip;
+  // RNAGAN_CONVD=0: off).  Only where the implicit-GEMM kernel would not split K either (>= 256 of its 512-row tiles): the
+  // split / no-split answer of the plan then does not depend on which of the two kernels runs.
+  if (lds_resident && rg_option("convd", 1) && !masked && s.bf16_out && s.mode == MODE_DOWN && s.nclass == 1 && s.taps == 16 &&
+      rg_convd_supported(M, Ncols, s.Cin, s.Hs, s.Ws) && M / 512 >= conv8_blocks_target())
+    return {RG_CK_PLANES, 1};
+  // the 64-column transposed conv with all four parity classes per block (conv8n_kernel).  Measured at batch 64
   // (128 -> 64 channels at 128 x 128): 161-168 us against 110-112 us for the one-class 256 x 64 kernel -- correct
   // (bit-identical) but slower: the layer re-reads every input pixel 16 times (4 classes x 4 taps) through LDS-DMA,
   // the 160 KB of LDS bound the bytes in flight per CU and one wave group issuing at a time halves them again.  Off
   // by default (RNAGAN_NARROW8=1 / rg_set_option("narrow8", 1) selects it); kept as the starting point of a kernel
   // that keeps the input patch resident in LDS instead of re-fetching it per tap.
-  // pp: the same layer with the input patch resident in LDS (rg_convp.hip; RNAGAN_CONVP=0: off)
-  if (rg_option("convp", RG_CONVP_DEFAULT) && !has_mask && bf16_out && mode == MODE_UP && nclass == 4 && taps == 4 && Ws > 0 &&
-      rg_convp_supported(M, Ncols, Cin, Hs, Ws)) {
-    pl.pp = true; pl.nsplit = 1; pl.bm = 256; pl.bn = 64;
-    return pl;
+  if (rg_option("narrow8", 0) && conv_up && Ncols == 64 && rg_is_pow2(cpt) && M >= 512) return {RG_CK_NARROW8, 1};
+  if (conv8_mode() && s.bf16_out && (s.mode == MODE_DOWN || s.mode == MODE_UP || s.mode == MODE_PLAIN) &&
+      (s.taps == 1 || rg_is_pow2(cpt)) && nkt >= 4 && nkt % 2 == 0 &&
+      ((Ncols % 256 == 0 && M >= 256) || (Ncols % 128 == 0 && M >= 512))) {
+    const RgConvKernel k = (Ncols % 256 == 0 && M >= 256) ? RG_CK_C8_256 : RG_CK_C8_512;
+    const KernelTile t = kernel_tile(k);
+    const long long tiles = (long long)((M + t.bm - 1) / t.bm) * (Ncols / t.bn) * s.nclass;
+    int ns = 1;
+    if (!masked)
+      while (tiles * ns < conv8_blocks_target() && ns < 8 && nkt % (ns * 4) == 0 && nkt / (ns * 2) >= 8) ns *= 2;
+    // conv8 = 1: only where the tile count fills the chip without split-K (measured at batch 64: with split-K the
+    // fp32 slabs of a 256x256 tile cost more than the pipeline gains; the 128x128 2-stage kernel splits less);
+    // conv8 & 4: also with split-K
+    if (ns == 1 || (conv8_mode() & 4)) return {k, ns};
   }
-  // pd: the 64 -> 128 channel stride-2 conv on a 128-pixel-wide input with its parity planes resident in LDS (rg_convd.hip;
-  // RNAGAN_CONVD=0: off).  Only where the implicit-GEMM kernel would not split K either (>= 256 of its 512-row tiles): the
-  // split / no-split answer of the plan queries then does not depend on which of the two kernels runs.
-  if (rg_option("convd", 1) && !masked && bf16_out && mode == MODE_DOWN && nclass == 1 && taps == 16 && Ws > 0 &&
-      rg_convd_supported(M, Ncols, Cin, Hs, Ws) && M / 512 >= conv8_blocks_target()) {
-    pl.pd = true; pl.nsplit = 1; pl.bm = 256; pl.bn = 128;
-    return pl;
+  // the 2-stage kernel
+  const int variant = rg_option("conv_tile", 1);
+  const long long tiles256 = (long long)((M + 255) / 256) * ((Ncols + 255) / 256) * s.nclass;
+  const bool narrow = Ncols <= 64;
+  const bool wide = !narrow && s.bf16_out && M >= 256 && Ncols >= 256 && Ncols % 256 == 0 &&
+                    (variant == 5 || (variant == 1 && tiles256 >= 256 && tiles256 % 256 == 0));
+  Pick p{narrow ? RG_CK_T256X64 : wide ? RG_CK_T256 : RG_CK_T128, 1};
+  if (!masked && wide) {
+    while (tiles256 * p.nsplit < 256 && p.nsplit < 8 && nkt / (p.nsplit * 2) >= 8) p.nsplit *= 2;   // one block per CU
+  } else if (!masked) {
+    p.nsplit = gather_split(M, Ncols, s.nclass, nkt, kernel_tile(p.kernel), s.bf16_out ? 4 : 16, s.bf16_out ? 16 : 8);
   }
-  if (rg_option("narrow8", 0) && bf16_out && mode == MODE_UP && nclass == 4 && Ncols == 64 && rg_is_pow2(cpt) && M >= 512) {
-    pl.n8 = true; pl.nsplit = 1; pl.bm = 512; pl.bn = 64;
-    return pl;
-  }
-  if (conv8_mode() && bf16_out && (mode == MODE_DOWN || mode == MODE_UP || mode == MODE_PLAIN) &&
-      (taps == 1 || rg_is_pow2(cpt))) {
-    int bm = 0, bn = 0;
-    if (Ncols % 256 == 0 && M >= 256) { bm = 256; bn = 256; }
-    else if (Ncols % 128 == 0 && M >= 512) { bm = 512; bn = 128; }
-    if (bm && nkt >= 4 && nkt % 2 == 0) {
-      const long long tiles = (long long)((M + bm - 1) / bm) * (Ncols / bn) * nclass;
-      int ns = 1;
-      if (!masked)
-        while (tiles * ns < conv8_blocks_target() && ns < 8 && nkt % (ns * 4) == 0 && nkt / (ns * 2) >= 8) ns *= 2;
-      // conv8 = 1: only where the tile count fills the chip without split-K (measured at batch 64: with split-K the
-      // fp32 slabs of a 256x256 tile cost more than the pipeline gains; the 128x128 2-stage kernel splits less);
-      // conv8 & 4: also with split-K
-      if (ns == 1 || (conv8_mode() & 4)) {
-        pl.c8 = true; pl.bm = bm; pl.bn = bn; pl.nsplit = ns;
-        return pl;
-      }
-    }
-  }
-  pl.narrow = Ncols <= 64;
-  const long long tiles256 = (long long)((M + 255) / 256) * ((Ncols + 255) / 256) * nclass;
-  pl.wide = !pl.narrow && bf16_out && M >= 256 && Ncols >= 256 && Ncols % 256 == 0 &&
-            (variant == 5 || (variant == 1 && tiles256 >= 256 && tiles256 % 256 == 0));
-  if (masked) {
-    pl.nsplit = 1;
-  } else if (pl.wide) {
-    pl.nsplit = 1;
-    while (tiles256 * pl.nsplit < 256 && pl.nsplit < 8 && nkt / (pl.nsplit * 2) >= 8) pl.nsplit *= 2;   // one block per CU
-  } else {
-    pl.nsplit = bf16_out ? gather_split(M, Ncols, nclass, nkt, true) : gather_split(M, Ncols, nclass, nkt, true, 16, 8);
-  }
+  // weight-streaming GEMMs (a batch of <= 64 rows against a large weight matrix: betaVAE layers, G.0): 64-row tile with a
+  // 3-deep DMA ring -- the bound is HBM latency x bytes in flight, not the matrix cores (RNAGAN_STREAM_TILE=0: off)
+  if (!narrow && !s.bf16_out && s.mode == MODE_PLAIN && M <= 64 && rg_option("stream_tile", 1)) p.kernel = RG_CK_STREAM64;
+  // the image layer of the resize-convolution generator (3 of 8 columns)
+  // (measured and rejected for the 64-column tile: 2 waves with 128 x 64 wave tiles, 147-154 us vs 109-112 us)
+  if (narrow && !s.bf16_out && s.mode == MODE_C3 && Ncols <= 32 && rg_option("narrow32", 1)) p.kernel = RG_CK_T256X64_N32;
+  return p;
+}
+
+// tile, slab16 and stats_rows follow from kernel and nsplit
+static void derive(RgConvPlan& pl, int M) {
+  const KernelTile t = kernel_tile(pl.kernel);
+  pl.bm = t.bm; pl.bn = t.bn;
+  // bf16 partial tiles (option slab16): only the 8-wave kernel writes them
+  pl.slab16 = (pl.nsplit > 1 && is_conv8(pl.kernel) && rg_option("slab16", RG_SLAB16_DEFAULT)) ? 1 : 0;
+  pl.stats_rows = (pl.nsplit > 1 || pl.kernel == RG_CK_LEGACY) ? 0 : pl.nclass * ((M + t.bm - 1) / t.bm) * (t.bm / t.wave_rows);
+}
+
+static RgConvPlan gather_plan(const GShape& s) {
+  RgConvPlan pl{};
+  pl.nclass = s.nclass; pl.a_bytes = s.a_bytes; pl.b_bytes = s.b_bytes;
+  Pick p = pick_kernel(s, true, s.masked);
+  // ws_bytes (see RgConvPlan): the slabs of the plan without the LDS-resident kernels and without a mask, legacy guard or not
+  const int ws_split = (s.masked || p.kernel == RG_CK_PATCH || p.kernel == RG_CK_PLANES) ? pick_kernel(s, false, false).nsplit
+                                                                                         : p.nsplit;
+  pl.ws_bytes = ws_split > 1 ? (size_t)ws_split * s.M * s.nclass * s.ld * sizeof(float) : 0;
+  if (use_v1() || !fits_descriptor(s.a_bytes) || !fits_descriptor(s.b_bytes)) p = {RG_CK_LEGACY, 1};
+  pl.kernel = p.kernel; pl.nsplit = p.nsplit;
+  derive(pl, s.M);
   return pl;
 }
 
-size_t rg_mfma_gather_ws_bytes(int mode, int M_out_rows, int M, int Ncols, int Cin, int taps, int nclass) {
-  const GPlan pl = gather_plan(mode, true, M, Ncols, Cin, taps, nclass, false);
-  return pl.nsplit > 1 ? (size_t)pl.nsplit * M_out_rows * Ncols * sizeof(float) : 0;
+// The plan as it runs when the caller's workspace cannot take the slabs of the plan as asked: unsplit, and then not on the
+// 8-wave kernel (whose tiles are sized for a grid that split-K fills) but on the 128 x 128 one.
+static RgConvPlan unsplit(RgConvPlan pl, int M) {
+  if (is_conv8(pl.kernel)) pl.kernel = RG_CK_T128;
+  pl.nsplit = 1; pl.ws_bytes = 0;
+  derive(pl, M);
+  return pl;
 }
 
+RgConvPlan rg_mfma_conv_plan(int up, int N, int Hlow, int Wlow, int O, int I, bool masked, bool dense_mask) {
+  GShape s{};
+  s.mode = up ? MODE_UP : MODE_DOWN; s.bf16_out = true;
+  s.M = N * Hlow * Wlow; s.Ncols = up ? I : O; s.Cin = up ? O : I; s.taps = up ? 4 : 16; s.nclass = up ? 4 : 1;
+  s.ld = s.Ncols; s.Hs = up ? Hlow : 2 * Hlow; s.Ws = up ? Wlow : 2 * Wlow;
+  s.a_bytes = (size_t)s.M * (up ? O : 4 * I) * 2; s.b_bytes = (size_t)O * 16 * I * 2;
+  s.masked = masked; s.dense_mask = dense_mask;
+  return gather_plan(s);
+}
 
-// partial rows the conv epilogue writes when asked for BatchNorm statistics (0: this launch cannot produce them)
-int rg_mfma_conv_stats_rows(int up, int N, int Hlow, int Wlow, int O, int I) {
-  const int M = N * Hlow * Wlow, Ncols = up ? I : O, Cin = up ? O : I, taps = up ? 4 : 16, nclass = up ? 4 : 1;
-  const size_t a_bytes = up ? (size_t)M * O * 2 : (size_t)M * 4 * I * 2, b_bytes = (size_t)O * 16 * I * 2;
-  if (use_v1() || a_bytes >= 0x7fffff00ull || b_bytes >= 0x7fffff00ull) return 0;
-  GPlan pl = gather_plan(up ? MODE_UP : MODE_DOWN, true, M, Ncols, Cin, taps, nclass, false, up ? Hlow : 2 * Hlow,
-                         up ? Wlow : 2 * Wlow);
-  if (pl.nsplit > 1) return 0;
-  if (pl.pp) return 4 * rg_convp_tiles(M) * 2;
-  if (pl.pd) return rg_convd_stats_rows(M);
-  if (pl.n8) return 4 * ((M + 511) / 512) * 8;
-  if (pl.c8) return nclass * ((M + pl.bm - 1) / pl.bm) * (pl.bm / 128);
-  const int bmm = (pl.narrow || pl.wide) ? 256 : 128, parts = pl.narrow ? 4 : 2;      // BM / wave-tile rows
-  return nclass * ((M + bmm - 1) / bmm) * parts;
+// its sibling for the launches that are no 4 x 4 stride-2 conv: one parity class, K = taps * Cin, rows of `ld` elements
+static RgConvPlan gemm_plan(int mode, bool bf16_out, int M, int Ncols, int Cin, int taps, int ld, size_t a_bytes = 0,
+                            size_t b_bytes = 0, bool masked = false) {
+  GShape s{};
+  s.mode = mode; s.bf16_out = bf16_out; s.M = M; s.Ncols = Ncols; s.Cin = Cin; s.taps = taps; s.nclass = 1; s.ld = ld;
+  s.a_bytes = a_bytes; s.b_bytes = b_bytes; s.masked = masked;
+  return gather_plan(s);
 }
 
 template <int MODE, int EPI>
-static int launch_gather2(const char* name, GArgs& g, int nclass, long long rows_out, size_t a_bytes, size_t b_bytes,
-                          void* ws, size_t ws_bytes, hipStream_t st) {
-  if (use_v1() || a_bytes >= 0x7fffff00ull || b_bytes >= 0x7fffff00ull) return launch_gather<MODE, EPI>(name, g, nclass, st);
-  G2Args a2{};
-  const GPlan pl = gather_plan(MODE, EPI == EPI_BF16, g.M, g.Ncols, g.Cin, g.taps, nclass, g.mask != nullptr || g.affine,
-                               g.Hs, g.Ws, g.mask != nullptr && !g.mask_packed);
-  const bool narrow = pl.narrow, wide = pl.wide;
-  int nsplit = pl.nsplit;
-  size_t need = (size_t)nsplit * rows_out * (EPI == EPI_BF16 ? g.Ncols : g.ldc) * sizeof(float);
-  if (nsplit > 1 && (!ws || ws_bytes < need)) nsplit = 1;
-  RG_REQUIRE(!g.defer_reduce || (nsplit > 1 && nsplit == pl.nsplit), RG_EUNSUPPORTED,
+static int launch_gather2(const char* name, GArgs& g, const RgConvPlan& asked, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int nclass = asked.nclass;
+  if (asked.kernel == RG_CK_LEGACY) return launch_gather<MODE, EPI>(name, g, nclass, st);
+  const bool no_slabs = asked.nsplit > 1 && (!ws || ws_bytes < asked.ws_bytes);
+  RG_REQUIRE(!g.defer_reduce || (asked.nsplit > 1 && !no_slabs), RG_EUNSUPPORTED,
              "%s: partial (split-K slab) output asked for a launch that does not split (rg_conv_split)", name);
-  if (EPI == EPI_LINEAR && (g.Ncols % 8 != 0 || g.ldc % 4 != 0)) nsplit = 1;      // slab rows are written 8 wide
+  const bool ragged = EPI == EPI_LINEAR && (g.Ncols % 8 != 0 || g.ldc % 4 != 0);      // slab rows are written 8 wide
+  const RgConvPlan pl = (no_slabs || (ragged && asked.nsplit > 1)) ? unsplit(asked, g.M) : asked;
+  const int nsplit = pl.nsplit;
+  const long long rows_out = (long long)g.M * nclass;
+  const size_t a_bytes = pl.a_bytes, b_bytes = pl.b_bytes;
+  G2Args a2{};
   a2.a_bytes = (unsigned)a_bytes; a2.b_bytes = (unsigned)b_bytes;
   a2.korder = (MODE == MODE_DOWN || MODE == MODE_UP) ? rg_option("korder", 1) : 0;
   a2.nsplit = nsplit; a2.slab = (float*)ws; a2.slab_stride = rows_out * (EPI == EPI_BF16 ? g.Ncols : g.ldc);
-  // weight-streaming GEMMs (a batch of <= 64 rows against a large weight matrix: betaVAE layers, G.0): 64-row tile with a
-  // 3-deep DMA ring -- the bound is HBM latency x bytes in flight, not the matrix cores (RNAGAN_STREAM_TILE=0: off)
-  const int stream_tile = rg_option("stream_tile", 1);
-  const bool stream = stream_tile && EPI == EPI_LINEAR && MODE == MODE_PLAIN && g.M <= 64 && !narrow;
-  const bool c8 = pl.c8 && nsplit == pl.nsplit;      // (a missing split-K workspace falls back to the 2-stage kernel)
-  // bf16 partial tiles (option slab16): only the 8-wave kernel writes them; rg_mfma_conv_slab16 answers the same for the consumer
-  a2.slab16 = (EPI == EPI_BF16 && nsplit > 1 && c8 && !pl.pp && !pl.pd && !pl.n8 && rg_option("slab16", RG_SLAB16_DEFAULT)) ? 1 : 0;
-  const int bn = c8 ? pl.bn : narrow ? 64 : wide ? 256 : 128, bmm = c8 ? pl.bm : stream ? 64 : (narrow || wide) ? 256 : 128;
-  g.tiles_n = (g.Ncols + bn - 1) / bn;
+  a2.slab16 = pl.slab16;
+  g.tiles_n = (g.Ncols + pl.bn - 1) / pl.bn;
   a2.g = g;
-  a2.tiles_m = (g.M + bmm - 1) / bmm;
-  dim3 grid(((g.M + bmm - 1) / bmm) * g.tiles_n, nclass, nsplit);
+  a2.tiles_m = (g.M + pl.bm - 1) / pl.bm;
+  dim3 grid(a2.tiles_m * g.tiles_n, nclass, nsplit);
   const int xcd = rg_option("xcd", 1), cfast = rg_option("class_fast", 1);
-  if (MODE == MODE_UP && nclass == 4 && cfast && a_bytes > b_bytes && !wide && (!c8 || conv8_mode() & 2)) {   // (measured: -4 % on the 256x256 tile)
+  if (MODE == MODE_UP && nclass == 4 && cfast && a_bytes > b_bytes && pl.kernel != RG_CK_T256 &&
+      (!is_conv8(pl.kernel) || conv8_mode() & 2)) {   // (measured: -4 % on the 256x256 tile)
     a2.class_fast = 1;
     grid = dim3(grid.x * 4, 1, nsplit);
   }
   a2.xcd_swizzle = (xcd && grid.x % 8 == 0 && grid.x >= 16 && (xcd == 2 || a_bytes > b_bytes)) ? 1 : 0;
-  // (measured and rejected for the 64-column tile: 2 waves with 128 x 64 wave tiles, 147-154 us vs 109-112 us)
-  RG_REQUIRE(!g.mask_packed || pl.pp, RG_EUNSUPPORTED, "%s: packed mask bits without the patch-resident kernel", name);
-  if (pl.pd) {
-    if constexpr (EPI == EPI_BF16 && MODE == MODE_DOWN) {
-      RG_REQUIRE(g.ldc == 128 && g.lgW == 6 && !g.mask && !g.affine && nsplit == 1, RG_EUNSUPPORTED, "%s: convd layout", name);
-      a2.g.tiles_n = 1;
-      a2.tiles_m = g.M / 256;
-      rg_convd_launch(&a2, st);
-    }
-  } else if (pl.pp) {
-    if constexpr (EPI == EPI_BF16 && MODE == MODE_UP) {
-      RG_REQUIRE(g.ldc == 64 && g.b_col == g.Cin, RG_EUNSUPPORTED, "%s: convp layout", name);
-      a2.g.tiles_n = 1;
-      a2.tiles_m = rg_convp_tiles(g.M);
-      rg_convp_launch(&a2, st);
-    }
-  } else if (pl.n8) {
-    if constexpr (EPI == EPI_BF16 && MODE == MODE_UP) {
-      a2.class_fast = 0;
-      a2.tiles_m = (g.M + 511) / 512;
-      a2.xcd_swizzle = (xcd && a2.tiles_m % 8 == 0 && a2.tiles_m >= 16) ? 1 : 0;
-      a2.lgcpt = rg_ilog2(g.Cin >> 6);
-      a2.cmask = (g.Cin >> 6) - 1;
-      a2.g.tiles_n = 1;
-      rg_conv8n_launch(&a2, (unsigned)a2.tiles_m, st);
-    }
-  } else if (c8) {
-    a2.lgcpt = g.taps == 1 ? 30 : rg_ilog2(g.Cin >> 6);
-    a2.cmask = g.taps == 1 ? 0x3fffffff : (g.Cin >> 6) - 1;
-    if constexpr (EPI == EPI_BF16 && (MODE == MODE_DOWN || MODE == MODE_UP || MODE == MODE_PLAIN))
-      rg_conv8_launch(MODE, &a2, pl.bm, grid.x, grid.y, grid.z, st);
-  } else if (stream) {
-    if constexpr (EPI == EPI_LINEAR && MODE == MODE_PLAIN)
-      hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 64, 128, 3, 128>), grid, dim3(128), 0, st, a2);
-  } else if (narrow) {
-    bool done = false;
-    if constexpr (MODE == MODE_C3 && EPI == EPI_LINEAR) {
-      if (g.Ncols <= 32 && rg_option("narrow32", 1)) {     // the image layer of the resize-convolution generator (3 of 8 columns)
-        hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 256, 64, 2, 256, 64, 0, 1>), grid, dim3(256), 0, st, a2);
-        done = true;
+  RG_REQUIRE(!g.mask_packed || pl.kernel == RG_CK_PATCH, RG_EUNSUPPORTED, "%s: packed mask bits without the patch-resident kernel", name);
+  switch (pl.kernel) {
+    case RG_CK_PLANES:           // (the two LDS-resident kernels lay out their own grid: rg_convd_launch / rg_convp_launch)
+      if constexpr (EPI == EPI_BF16 && MODE == MODE_DOWN) {
+        RG_REQUIRE(g.ldc == 128 && g.lgW == 6 && !g.mask && !g.affine && nsplit == 1, RG_EUNSUPPORTED, "%s: convd layout", name);
+        rg_convd_launch(&a2, st);
       }
-    }
-    if (!done) hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 256, 64, 2, 256>), grid, dim3(256), 0, st, a2);
-  } else if (wide) {
-    hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 256, 256, 2, 512, 128>), grid, dim3(512), 0, st, a2);
-  } else {
-    hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 128, 128, 2, 256>), grid, dim3(256), 0, st, a2);
+      break;
+    case RG_CK_PATCH:
+      if constexpr (EPI == EPI_BF16 && MODE == MODE_UP) {
+        RG_REQUIRE(g.ldc == 64 && g.b_col == g.Cin, RG_EUNSUPPORTED, "%s: convp layout", name);
+        rg_convp_launch(&a2, st);
+      }
+      break;
+    case RG_CK_NARROW8:
+      if constexpr (EPI == EPI_BF16 && MODE == MODE_UP) {
+        a2.class_fast = 0;
+        a2.xcd_swizzle = (xcd && a2.tiles_m % 8 == 0 && a2.tiles_m >= 16) ? 1 : 0;
+        a2.lgcpt = rg_ilog2(g.Cin >> 6);
+        a2.cmask = (g.Cin >> 6) - 1;
+        rg_conv8n_launch(&a2, (unsigned)a2.tiles_m, st);
+      }
+      break;
+    case RG_CK_C8_256: case RG_CK_C8_512:
+      a2.lgcpt = g.taps == 1 ? 30 : rg_ilog2(g.Cin >> 6);
+      a2.cmask = g.taps == 1 ? 0x3fffffff : (g.Cin >> 6) - 1;
+      if constexpr (EPI == EPI_BF16 && (MODE == MODE_DOWN || MODE == MODE_UP || MODE == MODE_PLAIN))
+        rg_conv8_launch(MODE, &a2, pl.bm, grid.x, grid.y, grid.z, st);
+      break;
+    case RG_CK_STREAM64:
+      if constexpr (EPI == EPI_LINEAR && MODE == MODE_PLAIN)
+        hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 64, 128, 3, 128>), grid, dim3(128), 0, st, a2);
+      break;
+    case RG_CK_T256X64_N32:
+      if constexpr (MODE == MODE_C3 && EPI == EPI_LINEAR)
+        hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 256, 64, 2, 256, 64, 0, 1>), grid, dim3(256), 0, st, a2);
+      break;
+    case RG_CK_T256X64:
+      hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 256, 64, 2, 256>), grid, dim3(256), 0, st, a2);
+      break;
+    case RG_CK_T256:
+      hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 256, 256, 2, 512, 128>), grid, dim3(512), 0, st, a2);
+      break;
+    default:                     // RG_CK_T128
+      hipLaunchKernelGGL((gather_gemm_dma_kernel<MODE, EPI, 128, 128, 2, 256>), grid, dim3(256), 0, st, a2);
   }
   RG_LAUNCH_CHECK(name);
   if (nsplit > 1 && EPI == EPI_LINEAR) {
@@ -1471,8 +1511,8 @@ int rg_mfma_conv_down(const void* x, const void* wdn, void* y, int N, int Hi, in
   int Ho = Hi / 2, Wo = Wi / 2;
   g.M = N * Ho * Wo; g.Ncols = O; g.Cin = I; g.taps = 16;
   g.lgW = rg_ilog2(Wo); g.lgH = rg_ilog2(Ho); g.Hs = Hi; g.Ws = Wi; g.ldc = O; g.b_col = 16 * I; g.b_tap = I;       // wdn[O][16][I]
-  return launch_gather2<MODE_DOWN, EPI_BF16>("conv_down(mfma)", g, 1, g.M, (size_t)N * Hi * Wi * I * 2,
-                                             (size_t)O * 16 * I * 2, ws, ws_bytes, st);
+  return launch_gather2<MODE_DOWN, EPI_BF16>("conv_down(mfma)", g, rg_mfma_conv_plan(0, N, Ho, Wo, O, I, mask || shift, mask != nullptr),
+                                             ws, ws_bytes, st);
 }
 
 int rg_mfma_conv_up(const void* x, const void* wup, void* y, int N, int Ho, int Wo, int O, int I, const void* mask,
@@ -1489,19 +1529,19 @@ int rg_mfma_conv_up(const void* x, const void* wup, void* y, int N, int Ho, int 
   g.A = (const uint16_t*)x; g.B = (const uint16_t*)wup; g.C = y;
   g.M = N * Ho * Wo; g.Ncols = I; g.Cin = O; g.taps = 4;
   g.lgW = rg_ilog2(Wo); g.lgH = rg_ilog2(Ho); g.Hs = Ho; g.Ws = Wo; g.ldc = I; g.b_col = O; g.b_tap = I * O;        // wup[16][I][O]
-  return launch_gather2<MODE_UP, EPI_BF16>("conv_up(mfma)", g, 4, (long long)g.M * 4, (size_t)N * Ho * Wo * O * 2,
-                                           (size_t)I * 16 * O * 2, ws, ws_bytes, st);
+  return launch_gather2<MODE_UP, EPI_BF16>("conv_up(mfma)", g, rg_mfma_conv_plan(1, N, Ho, Wo, O, I, mask || scale, mask && !mask_packed),
+                                           ws, ws_bytes, st);
 }
 
 bool rg_mfma_conv_up_maskbits_supported(int N, int Ho, int Wo, int O, int I) {
-  return rg_option("convp", RG_CONVP_DEFAULT) && rg_convp_supported(N * Ho * Wo, I, O, Ho, Wo) && (size_t)N * Ho * Wo * O * 2 < 0x7fffff00ull;
+  return rg_option("convp", RG_CONVP_DEFAULT) && rg_convp_supported(N * Ho * Wo, I, O, Ho, Wo) && fits_descriptor((size_t)N * Ho * Wo * O * 2);
 }
 
 // ---- fp32 mode, 64-column transposed conv on bf16 planes (rg_conv8f.hip): the 256 x 64 tile of the 2-stage kernel with an fp32
 // result; x planes [3][N][Ho][Wo][O], w planes wup[3][16][I][O], y fp32 [N][2Ho][2Wo][I]
 bool rg_mfma_conv_up_planes64_supported(int N, int Ho, int Wo, int O, int I, int products) {
   return (products == 3 || products == 6) && I == 64 && O % 64 == 0 && rg_is_pow2(Ho) && rg_is_pow2(Wo) && N * Ho * Wo >= 256 &&
-         3ull * N * Ho * Wo * O * 2 < 0x7fffff00ull;
+         fits_descriptor(3ull * N * Ho * Wo * O * 2);
 }
 int rg_mfma_conv_up_planes64(const void* xp, const void* wp, float* y, int N, int Ho, int Wo, int O, int I, int products,
                              hipStream_t st, const float* maskf, float mslope) {
@@ -1533,7 +1573,7 @@ bool rg_mfma_fp8_supported(int M, int K, int Ncols, int taps) {
   return (Ncols % 256 == 0 && M >= 256) || (Ncols % 128 == 0 && M >= 512);
 }
 static int launch_conv8_fp8(const char* name, int mode, GArgs& g, int nclass, size_t a_bytes, size_t b_bytes, hipStream_t st) {
-  RG_REQUIRE(a_bytes < 0x7fffff00ull && b_bytes < 0x7fffff00ull, RG_EUNSUPPORTED, "%s: operand of 2 GB or more", name);
+  RG_REQUIRE(fits_descriptor(a_bytes) && fits_descriptor(b_bytes), RG_EUNSUPPORTED, "%s: operand of 2 GB or more", name);
   G2Args a2{};
   const int bm = g.Ncols % 256 == 0 && g.M >= 256 ? 256 : 512, bn = bm == 256 ? 256 : 128;
   g.in_fp8 = 1;
@@ -1569,33 +1609,6 @@ int rg_mfma_gemm_fp8(const void* a8, const void* b8, void* y, int M, int K, int 
   return launch_conv8_fp8("gemm_fp8", MODE_PLAIN, g, 1, (size_t)M * K, (size_t)Ncols * K, st);
 }
 
-// split factor of the plain (unmasked, bf16-output) conv launch of this shape: > 1 means the launch leaves fp32 slabs
-// [nsplit][rows_out][Ncols] that a reduction pass (or a fused consumer, rg_splitbn.hip) sums
-int rg_mfma_conv_nsplit(int up, int N, int Hlow, int Wlow, int O, int I) {
-  const int M = N * Hlow * Wlow, Ncols = up ? I : O, Cin = up ? O : I, taps = up ? 4 : 16, nclass = up ? 4 : 1;
-  const size_t a_bytes = up ? (size_t)M * O * 2 : (size_t)M * 4 * I * 2, b_bytes = (size_t)O * 16 * I * 2;
-  if (use_v1() || a_bytes >= 0x7fffff00ull || b_bytes >= 0x7fffff00ull) return 1;
-  const GPlan pl = gather_plan(up ? MODE_UP : MODE_DOWN, true, M, Ncols, Cin, taps, nclass, false, up ? Hlow : 2 * Hlow,
-                               up ? Wlow : 2 * Wlow);
-  return pl.nsplit;
-}
-
-// 1: the split-K launch of this layer (rg_conv_*_partial, no mask / affine) leaves bf16 partial tiles (launch_gather2: slab16)
-int rg_mfma_conv_slab16(int up, int N, int Hlow, int Wlow, int O, int I) {
-  const int M = N * Hlow * Wlow, Ncols = up ? I : O, Cin = up ? O : I, taps = up ? 4 : 16, nclass = up ? 4 : 1;
-  const size_t a_bytes = up ? (size_t)M * O * 2 : (size_t)M * 4 * I * 2, b_bytes = (size_t)O * 16 * I * 2;
-  if (use_v1() || a_bytes >= 0x7fffff00ull || b_bytes >= 0x7fffff00ull) return 0;
-  const GPlan pl = gather_plan(up ? MODE_UP : MODE_DOWN, true, M, Ncols, Cin, taps, nclass, false, up ? Hlow : 2 * Hlow,
-                               up ? Wlow : 2 * Wlow);
-  return (pl.nsplit > 1 && pl.c8 && !pl.pp && !pl.pd && !pl.n8 && rg_option("slab16", RG_SLAB16_DEFAULT)) ? 1 : 0;
-}
-
-size_t rg_mfma_conv_ws_bytes(int up, int N, int Hlow, int Wlow, int O, int I) {
-  int M = N * Hlow * Wlow;
-  if (up) return rg_mfma_gather_ws_bytes(MODE_UP, M * 4, M, I, O, 4, 4);
-  return rg_mfma_gather_ws_bytes(MODE_DOWN, M, M, O, I, 16, 1);
-}
-
 int rg_mfma_gemm_plain(const void* a, const void* bt, void* c, int M, int K, int Ncols, int ldc, hipStream_t st,
                        const float* scale, const float* shift, float slope) {
   GArgs g{};
@@ -1603,47 +1616,46 @@ int rg_mfma_gemm_plain(const void* a, const void* bt, void* c, int M, int K, int
   g.A = (const uint16_t*)a; g.B = (const uint16_t*)bt; g.C = c;
   g.M = M; g.Ncols = Ncols; g.Cin = K; g.taps = 1; g.lgW = 0; g.lgH = 0; g.Hs = 1; g.Ws = 1; g.ldc = ldc; g.b_col = K; g.b_tap = 0;
   RG_REQUIRE(ldc == Ncols, RG_EINVAL, "gemm_plain: dense output expected");
-  return launch_gather2<MODE_PLAIN, EPI_BF16>("gemm_plain(mfma)", g, 1, M, (size_t)M * K * 2, (size_t)Ncols * K * 2,
-                                              nullptr, 0, st);
+  return launch_gather2<MODE_PLAIN, EPI_BF16>("gemm_plain(mfma)", g, gemm_plan(MODE_PLAIN, true, M, Ncols, K, 1, Ncols, (size_t)M * K * 2,
+                                                                                  (size_t)Ncols * K * 2, g.affine != 0), nullptr, 0, st);
 }
 
 size_t rg_mfma_linear_ws_bytes(int M, int Kpad, int Nout) {
-  int s = gather_split(M, Nout, 1, Kpad >> 6, true, 16, 8);
-  return s > 1 ? (size_t)s * M * Nout * sizeof(float) : 0;
+  return gemm_plan(MODE_PLAIN, false, M, Nout, Kpad, 1, Nout).ws_bytes;
 }
 
 int rg_mfma_linear(const void* a, const void* bt, const float* scale, const float* shift, float* y, int ldy, int M,
                    int Kpad, int Nout, float slope, void* ws, size_t ws_bytes, hipStream_t st) {
   RG_REQUIRE(Kpad % 64 == 0, RG_EUNSUPPORTED, "linear(mfma): K_pad %% 64 required");
   // ragged widths (Nout % 8 != 0) are an epilogue feature of the LDS-DMA kernel only (operands below 2 GB)
-  RG_REQUIRE(Nout % 8 == 0 || (!use_v1() && (size_t)M * Kpad * 2 < 0x7fffff00ull && (size_t)Nout * Kpad * 2 < 0x7fffff00ull),
+  const RgConvPlan pl = gemm_plan(MODE_PLAIN, false, M, Nout, Kpad, 1, ldy, (size_t)M * Kpad * 2, (size_t)Nout * Kpad * 2);
+  RG_REQUIRE(Nout % 8 == 0 || pl.kernel != RG_CK_LEGACY,
              RG_EUNSUPPORTED, "linear(mfma): Nout %% 8 required for operands of 2 GB and more");
   GArgs g{};
   g.A = (const uint16_t*)a; g.B = (const uint16_t*)bt; g.C = y;
   g.M = M; g.Ncols = Nout; g.Cin = Kpad; g.taps = 1; g.lgW = 0; g.lgH = 0; g.Hs = 1; g.Ws = 1; g.ldc = ldy; g.b_col = Kpad; g.b_tap = 0;
   g.scale = scale; g.shift = shift; g.slope = slope;
-  return launch_gather2<MODE_PLAIN, EPI_LINEAR>("linear(mfma)", g, 1, M, (size_t)M * Kpad * 2, (size_t)Nout * Kpad * 2,
-                                                ws, ws_bytes, st);
+  return launch_gather2<MODE_PLAIN, EPI_LINEAR>("linear(mfma)", g, pl, ws, ws_bytes, st);
 }
 
 bool rg_mfma_wgrad_supported(int N, int Ho, int Wo, int O, int I) {
   return N > 0 && rg_is_pow2(Ho) && rg_is_pow2(Wo) && O % 128 == 0 && I % 64 == 0;
 }
-static int mfma_wgrad_split(int N, int Ho, int Wo, int O, int I) {
+// split-K of the two 128 x 128-tile kernels: `target` blocks, at least 256 pixels per split
+static int wgrad_split128(int K, int O, int I, int target) {
   int tiles = (O / 128) * (16 * I / 128);
-  int K = N * Ho * Wo;
-  int want = (768 + tiles - 1) / tiles;
+  int want = (target + tiles - 1) / tiles;
   int maxs = K / 256;
   if (maxs < 1) maxs = 1;
   int s = want < maxs ? want : maxs;
   return s < 1 ? 1 : s;
 }
 size_t rg_mfma_wgrad_ws_bytes(int N, int Ho, int Wo, int O, int I) {
-  return (size_t)mfma_wgrad_split(N, Ho, Wo, O, I) * O * I * 16 * sizeof(float);
+  return (size_t)wgrad_split128(N * Ho * Wo, O, I, 768) * O * I * 16 * sizeof(float);
 }
 int rg_mfma_conv_wgrad(const void* low, const void* high, float* dw, int N, int Ho, int Wo, int O, int I,
                        int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
-  int nsplit = mfma_wgrad_split(N, Ho, Wo, O, I);
+  int nsplit = wgrad_split128(N * Ho * Wo, O, I, 768);
   size_t elems = (size_t)O * I * 16;
   RG_REQUIRE(ws && ws_bytes >= (size_t)nsplit * elems * sizeof(float), RG_EWORKSPACE,
              "conv_wgrad(mfma): workspace too small");
@@ -1659,16 +1671,44 @@ int rg_mfma_conv_wgrad(const void* low, const void* high, float* dw, int N, int 
   return rg_reduce_slabs((const float*)ws, dw, elems, nsplit, accumulate, 0, 0, st);
 }
 
-static int mfma_wgrad_split_k(int K, int O, int I) {
-  // 2 blocks are resident per CU: a grid of 512 (or a multiple) fills the 256 CUs without a half-empty last round
-  const int target = rg_option("wgrad_blocks", 512);
-  int tiles = (O / 128) * (16 * I / 128);
-  int want = (target + tiles - 1) / tiles;
-  int maxs = K / 256;
-  if (maxs < 1) maxs = 1;
-  int s = want < maxs ? want : maxs;
-  return s < 1 ? 1 : s;
+// ---- the weight-gradient plan (RgWgradPlan, rg_internal.h): read by rg_mfma_conv_wgrad2, by the fused gradient + Adam and
+// wire launches and by the queries of rg_api.hip (rg_conv_wgrad_workspace_bytes, rg_conv_wgrad_adam_supported).
+// ping_pong = false: the plan of the DMA kernel alone -- what a launch falls back to when its workspace cannot take the slabs
+static RgWgradPlan wgrad_plan(int Kseg, bool two, int O, int I, bool ping_pong) {
+  const int K = two ? 2 * Kseg : Kseg;
+  const size_t slab = (size_t)O * I * 16 * sizeof(float);
+  // the DMA kernel: 2 blocks are resident per CU, a grid of 512 (or a multiple) fills the 256 CUs without a half-empty last round
+  const int dma_split = wgrad_split128(K, O, I, rg_option("wgrad_blocks", 512));
+  // the 8-wave ping-pong kernel (rg_wgrad8.hip) or its 128 x 512 form (O = 128 layers), whichever takes the shape
+  RgWgradKernel k8 = RG_WK_DMA;
+  int ns8 = 0, per8 = 0;
+  if (rg_wgrad8_supported(K, O, I)) { k8 = RG_WK_WGRAD8; ns8 = rg_wgrad8_split(K, O, I, 256, 256, &per8); }
+  else if (rg_wgrad8n_supported(K, O, I)) { k8 = RG_WK_WGRAD8N; ns8 = rg_wgrad8_split(K, O, I, 128, 512, &per8); }
+  RgWgradPlan pl{};
+  pl.ws_bytes = (size_t)(ns8 > dma_split ? ns8 : dma_split) * slab;
+  const int opt8 = rg_option("wgrad8", 1), opt8n = rg_option("wgrad8n", 1);
+  // (measured, batch 64: where the 128 x 128 kernel needs no split-K but the 256 x 256 one does -- 128 tiles of 256 x 256 --
+  // a single segment is faster there: 76 vs 83 us, no slab pass; with two segments the longer k-loop wins back)
+  // (at twice the pixels -- the batched D step -- the longer k-loop wins there too: 134 vs 141 us)
+  const bool old_direct = dma_split == 1 && ns8 > 1 && !two && K < 8192 && opt8 == 1;
+  // wgrad8n = 2: only for K >= 2^19 pixels (two segments / batch 128)
+  const bool take8 = k8 == RG_WK_WGRAD8 ? opt8 && !old_direct : k8 == RG_WK_WGRAD8N && opt8n && (opt8n != 2 || K >= (1 << 19));
+  if (use_v1() || !fits_descriptor((size_t)Kseg * O * 2) || !fits_descriptor((size_t)Kseg * 4 * I * 2) || (two && Kseg % 64 != 0)) {
+    pl.kernel = RG_WK_LEGACY;
+    pl.nsplit = wgrad_split128(Kseg, O, I, 768);
+    pl.slab_bytes = pl.nsplit * slab;
+  } else if (ping_pong && take8) {
+    pl.kernel = k8; pl.nsplit = ns8; pl.kt_per_split = per8;
+    pl.slab_bytes = ns8 * slab;
+  } else {
+    pl.kernel = RG_WK_DMA;
+    pl.slab_bytes = dma_split * slab;        // (before the split is rounded to whole 64-pixel k-tiles)
+    pl.kt_per_split = ((K + dma_split - 1) / dma_split + 63) / 64;
+    pl.nsplit = (K + 64 * pl.kt_per_split - 1) / (64 * pl.kt_per_split);
+  }
+  return pl;
 }
+RgWgradPlan rg_mfma_wgrad_plan(int Kseg, bool two, int O, int I) { return wgrad_plan(Kseg, two, O, I, true); }
 
 // nsplit_out (optional): the split-K launch leaves its fp32 slabs [nsplit][O][16][I] in `ws` and the REDUCTION IS SKIPPED
 // (*nsplit_out = nsplit > 1; dw untouched) -- the caller's optimizer step sums the slabs itself (rg_adam_step_slabs); a plan
@@ -1678,117 +1718,68 @@ int rg_mfma_conv_wgrad2(const void* low0, const void* high0, const void* low1, c
                         int* nsplit_out, int* slab_dtype_out) {
   if (nsplit_out) *nsplit_out = 1;
   if (slab_dtype_out) *slab_dtype_out = RG_F32;
-  // slabs LEFT to the caller may be bf16 (the two ping-pong kernels; option wslab16): each partial sum rounded once, added in
-  // fp32 by rg_adam_step_slabs -- half the bytes written here and read there
-  const int s16 = (nsplit_out && slab_dtype_out && rg_option("wslab16", RG_WSLAB16_DEFAULT)) ? 1 : 0;
   const int Kseg = N * Ho * Wo;
   const bool two = low1 != nullptr;
-  size_t lowb = (size_t)Kseg * O * 2, highb = (size_t)Kseg * 4 * I * 2;
-  if (use_v1() || lowb >= 0x7fffff00ull || highb >= 0x7fffff00ull || (two && Kseg % 64 != 0)) {
+  RgWgradPlan pl = wgrad_plan(Kseg, two, O, I, true);
+  const bool ping_pong = pl.kernel == RG_WK_WGRAD8 || pl.kernel == RG_WK_WGRAD8N;
+  if (ping_pong && pl.nsplit > 1 && !(ws && ws_bytes >= pl.slab_bytes)) pl = wgrad_plan(Kseg, two, O, I, false);
+  if (pl.kernel == RG_WK_LEGACY) {
     int rc = rg_mfma_conv_wgrad(low0, high0, dw, N, Ho, Wo, O, I, accumulate, ws, ws_bytes, st);
     if (rc || !two) return rc;
     return rg_mfma_conv_wgrad(low1, high1, dw, N, Ho, Wo, O, I, 1, ws, ws_bytes, st);
   }
-  const int K = two ? 2 * Kseg : Kseg;
-  size_t elems = (size_t)O * I * 16;
-  if (rg_option("wgrad8", 1) && rg_wgrad8_supported(K, O, I)) {        // 8-wave ping-pong kernel (rg_wgrad8.hip)
-    int per = 0;
-    const int ns = rg_wgrad8_split(K, O, I, &per);
-    // (measured, batch 64: where the 128 x 128 kernel needs no split-K but this one does -- 128 tiles of 256 x 256 --
-    // a single segment is faster there: 76 vs 83 us, no slab pass; with two segments the longer k-loop wins back)
-    // (at twice the pixels -- the batched D step -- the longer k-loop wins there too: 134 vs 141 us)
-    const bool old_direct = mfma_wgrad_split_k(K, O, I) == 1 && ns > 1 && !two && K < 8192 && rg_option("wgrad8", 1) == 1;
-    if (!old_direct && (ns == 1 || (ws && ws_bytes >= (size_t)ns * elems * sizeof(float)))) {
-      int rc = rg_wgrad8_launch(low0, high0, low1, high1, ns == 1 ? dw : (float*)ws, Kseg, two ? 1 : 0, O, I, Ho, Wo, ns,
-                                per, accumulate, st, s16);
-      if (rc || ns == 1) return rc;
-      if (nsplit_out) { *nsplit_out = ns; if (s16) *slab_dtype_out = RG_H16; return RG_OK; }
-      return rg_reduce_slabs((const float*)ws, dw, elems, ns, accumulate, 0, 0, st);
-    }
+  const int nsplit = pl.nsplit;
+  // slabs LEFT to the caller may be bf16 (the two ping-pong kernels; option wslab16): each partial sum rounded once, added in
+  // fp32 by rg_adam_step_slabs -- half the bytes written here and read there
+  const int s16 = (pl.kernel != RG_WK_DMA && nsplit_out && slab_dtype_out && rg_option("wslab16", RG_WSLAB16_DEFAULT)) ? 1 : 0;
+  if (pl.kernel != RG_WK_DMA) {
+    int rc = (pl.kernel == RG_WK_WGRAD8 ? rg_wgrad8_launch : rg_wgrad8n_launch)(
+        low0, high0, low1, high1, nsplit == 1 ? dw : (float*)ws, Kseg, two ? 1 : 0, O, I, Ho, Wo, nsplit, pl.kt_per_split,
+        accumulate, st, s16);
+    if (rc) return rc;
+  } else {
+    RG_REQUIRE(ws && ws_bytes >= pl.slab_bytes, RG_EWORKSPACE, "conv_wgrad(mfma): workspace too small");
+    W2Args g{};
+    g.low[0] = (const uint16_t*)low0; g.high[0] = (const uint16_t*)high0;
+    g.low[1] = (const uint16_t*)(two ? low1 : low0); g.high[1] = (const uint16_t*)(two ? high1 : high0);
+    g.low_bytes[0] = g.low_bytes[1] = (unsigned)((size_t)Kseg * O * 2);
+    g.high_bytes[0] = g.high_bytes[1] = (unsigned)((size_t)Kseg * 4 * I * 2);
+    g.Kseg[0] = Kseg; g.Kseg[1] = two ? Kseg : 0;
+    g.slab = (float*)ws; g.O = O; g.I = I;
+    g.lgWo = rg_ilog2(Wo); g.lgHo = rg_ilog2(Ho); g.Hh = 2 * Ho; g.Wh = 2 * Wo;
+    g.tiles_c = 16 * I / 128;
+    g.klen = 64 * pl.kt_per_split;
+    g.tiles_o = O / 128; g.nsplit = nsplit;
+    // dW is tap-major [O][16][I] = the slab layout: a single split writes (or adds to) dW straight from its epilogue
+    if (nsplit == 1) { g.slab = dw; g.accumulate = accumulate; }
+    hipLaunchKernelGGL(wgrad_dma_kernel<false>, dim3((unsigned)(g.tiles_o * g.tiles_c * nsplit)), dim3(256), 0, st, g);
+    RG_LAUNCH_CHECK("conv_wgrad(mfma)");
   }
-  // the 128 x 512 form of that kernel (O = 128 layers); option value 2: only for K >= 2^19 pixels (two segments / batch 128)
-  if (rg_option("wgrad8n", 1) && rg_wgrad8n_supported(K, O, I) && (rg_option("wgrad8n", 1) != 2 || K >= (1 << 19))) {
-    int per = 0;
-    const int ns = rg_wgrad8n_split(K, O, I, &per);
-    if (ns == 1 || (ws && ws_bytes >= (size_t)ns * elems * sizeof(float))) {
-      int rc = rg_wgrad8n_launch(low0, high0, low1, high1, ns == 1 ? dw : (float*)ws, Kseg, two ? 1 : 0, O, I, Ho, Wo, ns,
-                                 per, accumulate, st, s16);
-      if (rc || ns == 1) return rc;
-      if (nsplit_out) { *nsplit_out = ns; if (s16) *slab_dtype_out = RG_H16; return RG_OK; }
-      return rg_reduce_slabs((const float*)ws, dw, elems, ns, accumulate, 0, 0, st);
-    }
-  }
-  int nsplit = mfma_wgrad_split_k(K, O, I);
-  RG_REQUIRE(ws && ws_bytes >= (size_t)nsplit * elems * sizeof(float), RG_EWORKSPACE,
-             "conv_wgrad(mfma): workspace too small");
-  W2Args g{};
-  g.low[0] = (const uint16_t*)low0; g.high[0] = (const uint16_t*)high0;
-  g.low[1] = (const uint16_t*)(two ? low1 : low0); g.high[1] = (const uint16_t*)(two ? high1 : high0);
-  g.low_bytes[0] = g.low_bytes[1] = (unsigned)lowb; g.high_bytes[0] = g.high_bytes[1] = (unsigned)highb;
-  g.Kseg[0] = Kseg; g.Kseg[1] = two ? Kseg : 0;
-  g.slab = (float*)ws; g.O = O; g.I = I;
-  g.lgWo = rg_ilog2(Wo); g.lgHo = rg_ilog2(Ho); g.Hh = 2 * Ho; g.Wh = 2 * Wo;
-  g.tiles_c = 16 * I / 128;
-  int klen = (K + nsplit - 1) / nsplit;
-  g.klen = (klen + 63) / 64 * 64;
-  nsplit = (K + g.klen - 1) / g.klen;
-  g.tiles_o = O / 128; g.nsplit = nsplit;
-  // dW is tap-major [O][16][I] = the slab layout: a single split writes (or adds to) dW straight from its epilogue
-  if (nsplit == 1) { g.slab = dw; g.accumulate = accumulate; }
-  hipLaunchKernelGGL(wgrad_dma_kernel<false>, dim3((unsigned)(g.tiles_o * g.tiles_c * nsplit)), dim3(256), 0, st, g);
-  RG_LAUNCH_CHECK("conv_wgrad(mfma)");
   if (nsplit == 1) return RG_OK;
-  if (nsplit_out) { *nsplit_out = nsplit; return RG_OK; }
-  return rg_reduce_slabs((const float*)ws, dw, elems, nsplit, accumulate, 0, 0, st);
+  if (nsplit_out) { *nsplit_out = nsplit; if (s16) *slab_dtype_out = RG_H16; return RG_OK; }
+  return rg_reduce_slabs((const float*)ws, dw, (size_t)O * I * 16, nsplit, accumulate, 0, 0, st);
 }
 
 // ---- weight gradient + optimizer step in one launch: the plans of rg_mfma_conv_wgrad2 that run wgrad8_kernel WITHOUT split-K
 // (the two 33.5 M-parameter layers at batch 64: D.5 and G.1, 512 tiles) can apply Adam to their tile where it sits in LDS
 // instead of writing 4 bytes per parameter that the streaming Adam reads back.
-bool rg_mfma_conv_wgrad_adam_supported(int N, int Ho, int Wo, int O, int I, bool two) {
-  const int Kseg = N * Ho * Wo;
-  const size_t lowb = (size_t)Kseg * O * 2, highb = (size_t)Kseg * 4 * I * 2;
-  if (use_v1() || lowb >= 0x7fffff00ull || highb >= 0x7fffff00ull || (two && Kseg % 64 != 0)) return false;
-  const int K = two ? 2 * Kseg : Kseg;
-  if (!rg_option("wgrad8", 1) || !rg_wgrad8_supported(K, O, I)) return false;
-  int per = 0;
-  return rg_wgrad8_split(K, O, I, &per) == 1;
-}
 int rg_mfma_conv_wgrad_adam(const void* low0, const void* high0, const void* low1, const void* high1, int N, int Ho, int Wo,
                             int O, int I, float* p, float* m, float* v, uint16_t* shadow, const float* hyper, hipStream_t st) {
   const bool two = low1 != nullptr;
-  RG_REQUIRE(rg_mfma_conv_wgrad_adam_supported(N, Ho, Wo, O, I, two), RG_EUNSUPPORTED,
+  const RgWgradPlan pl = wgrad_plan(N * Ho * Wo, two, O, I, true);
+  RG_REQUIRE(pl.kernel == RG_WK_WGRAD8 && pl.nsplit == 1, RG_EUNSUPPORTED,
              "conv_wgrad_adam: no single-split plan of the 256 x 256 kernel for this shape");
-  int per = 0;
-  rg_wgrad8_split((two ? 2 : 1) * N * Ho * Wo, O, I, &per);
-  return rg_wgrad8_adam_launch(low0, high0, low1, high1, N * Ho * Wo, two ? 1 : 0, O, I, Ho, Wo, per, p, m, v, shadow, hyper, st);
+  return rg_wgrad8_adam_launch(low0, high0, low1, high1, N * Ho * Wo, two ? 1 : 0, O, I, Ho, Wo, pl.kt_per_split, p, m, v, shadow,
+                               hyper, st);
 }
 
 int rg_mfma_conv_wgrad_wire(const void* low0, const void* high0, const void* low1, const void* high1, int N, int Ho, int Wo,
                             int O, int I, uint16_t* out16, hipStream_t st) {
   const bool two = low1 != nullptr;
-  RG_REQUIRE(rg_mfma_conv_wgrad_adam_supported(N, Ho, Wo, O, I, two), RG_EUNSUPPORTED,
+  const RgWgradPlan pl = wgrad_plan(N * Ho * Wo, two, O, I, true);
+  RG_REQUIRE(pl.kernel == RG_WK_WGRAD8 && pl.nsplit == 1, RG_EUNSUPPORTED,
              "conv_wgrad_wire: no single-split plan of the 256 x 256 kernel for this shape");
-  int per = 0;
-  rg_wgrad8_split((two ? 2 : 1) * N * Ho * Wo, O, I, &per);
-  return rg_wgrad8_wire_launch(low0, high0, low1, high1, out16, N * Ho * Wo, two ? 1 : 0, O, I, Ho, Wo, per, st);
-}
-
-size_t rg_mfma_wgrad2_ws_bytes(int N, int Ho, int Wo, int O, int I) {
-  size_t a = (size_t)mfma_wgrad_split_k(N * Ho * Wo, O, I) * O * I * 16 * sizeof(float);
-  size_t b = (size_t)mfma_wgrad_split_k(2 * N * Ho * Wo, O, I) * O * I * 16 * sizeof(float);
-  size_t m = a > b ? a : b;
-  for (int k = 1; k <= 2; ++k)
-    if (rg_wgrad8_supported(k * N * Ho * Wo, O, I)) {
-      int per = 0;
-      const size_t c = (size_t)rg_wgrad8_split(k * N * Ho * Wo, O, I, &per) * O * I * 16 * sizeof(float);
-      if (c > m) m = c;
-    } else if (rg_wgrad8n_supported(k * N * Ho * Wo, O, I)) {
-      int per = 0;
-      const size_t c = (size_t)rg_wgrad8n_split(k * N * Ho * Wo, O, I, &per) * O * I * 16 * sizeof(float);
-      if (c > m) m = c;
-    }
-  return m;
+  return rg_wgrad8_wire_launch(low0, high0, low1, high1, out16, N * Ho * Wo, two ? 1 : 0, O, I, Ho, Wo, pl.kt_per_split, st);
 }
 
 int rg_mfma_pack_conv_weight(const float* w, void* wdn, void* wup, int O, int I, hipStream_t st) {
@@ -1921,11 +1912,11 @@ __global__ void pack_w3_kernel(const float* __restrict__ w, uint16_t* __restrict
 bool rg_mfma_upconv3_supported(int N, int H, int W, int Cin, int Cout) {
   const long long M = (long long)N * 4 * H * W;
   return Cin % 64 == 0 && Cout % 8 == 0 && rg_is_pow2(H) && rg_is_pow2(W) && M < 0x7fffffffLL && !use_v1() &&
-         (size_t)N * (2 * H + 2) * (2 * W + 2) * Cin * 2 < 0x7fffff00ull;
+         fits_descriptor((size_t)N * (2 * H + 2) * (2 * W + 2) * Cin * 2);
 }
 size_t rg_mfma_upconv3_fwd_ws_bytes(int N, int H, int W, int Cin, int Cout) {
   return rg_align_up((size_t)N * (2 * H + 2) * (2 * W + 2) * Cin * 2, 256) + rg_align_up((size_t)Cout * 9 * Cin * 2, 256) +
-         rg_mfma_gather_ws_bytes(MODE_C3, N * 4 * H * W, N * 4 * H * W, Cout, Cin, 9, 1);
+         gemm_plan(MODE_C3, true, N * 4 * H * W, Cout, Cin, 9, Cout).ws_bytes;
 }
 int rg_mfma_upconv3_fwd(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int Cin,
                         int Cout, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -1944,8 +1935,9 @@ int rg_mfma_upconv3_fwd(const void* x, const float* w, const float* bias, void* 
   g.M = N * 4 * H * W; g.Ncols = Cout; g.Cin = Cin; g.taps = 9;
   g.lgW = rg_ilog2(2 * W); g.lgH = rg_ilog2(2 * H); g.Hs = Hp; g.Ws = Wp; g.ldc = Cout; g.b_col = 9 * Cin; g.b_tap = Cin;
   g.shift = bias;
-  return launch_gather2<MODE_C3, EPI_BF16>("upconv3_fwd(mfma)", g, 1, g.M, (size_t)N * Hp * Wp * Cin * 2,
-                                           (size_t)Cout * 9 * Cin * 2, (char*)ws + padb + wpb, ws_bytes - padb - wpb, st);
+  return launch_gather2<MODE_C3, EPI_BF16>("upconv3_fwd(mfma)", g, gemm_plan(MODE_C3, true, g.M, Cout, Cin, 9, Cout, (size_t)N * Hp * Wp * Cin * 2,
+                                                                             (size_t)Cout * 9 * Cin * 2),
+                                           (char*)ws + padb + wpb, ws_bytes - padb - wpb, st);
 }
 
 // ---- the generator's image block (Cout <= 8, NCHW fp32 out): same pad + 9-tap GEMM with the output columns padded
@@ -1986,8 +1978,8 @@ int rg_mfma_upconv3_image_fwd(const void* x, const float* w, const float* bias, 
   g.M = N * 4 * H * W; g.Ncols = Cout; g.Cin = Cin; g.taps = 9;
   g.lgW = rg_ilog2(2 * W); g.lgH = rg_ilog2(2 * H); g.Hs = Hp; g.Ws = Wp; g.ldc = 8; g.b_col = 9 * Cin; g.b_tap = Cin;
   g.slope = 1.0f;
-  int rc = launch_gather2<MODE_C3, EPI_LINEAR>("upconv3_fwd(mfma, image)", g, 1, g.M, (size_t)N * Hp * Wp * Cin * 2,
-                                               (size_t)Cout * 9 * Cin * 2, nullptr, 0, st);
+  int rc = launch_gather2<MODE_C3, EPI_LINEAR>("upconv3_fwd(mfma, image)", g, gemm_plan(MODE_C3, false, g.M, Cout, Cin, 9, 8, (size_t)N * Hp * Wp * Cin * 2,
+                                                                                        (size_t)Cout * 9 * Cin * 2), nullptr, 0, st);
   if (rc) return rc;
   hipLaunchKernelGGL(rows8_to_nchw_kernel, dim3(grid_cap((size_t)g.M)), dim3(256), 0, st, tmp, bias, y, Cout,
                      (unsigned)(4 * H * W), (size_t)g.M);
@@ -2062,7 +2054,7 @@ bool rg_mfma_upconv3_bwd_supported(int N, int H, int W, int Cin, int Cout) {
 size_t rg_mfma_upconv3_bwd_ws_bytes(int N, int H, int W, int Cin, int Cout) {
   const int Mp = N * (2 * H + 2) * (2 * W + 2);
   return rg_align_up((size_t)Mp * Cin * 2, 256) + rg_align_up((size_t)Cout * 9 * Cin * 2, 256) +
-         rg_mfma_gather_ws_bytes(MODE_C3T, Mp, Mp, Cin, Cout, 9, 1);
+         gemm_plan(MODE_C3T, true, Mp, Cin, Cout, 9, Cin).ws_bytes;
 }
 int rg_mfma_upconv3_bwd_data(const void* gy, const float* w, void* gx, int N, int H, int W, int Cin, int Cout, void* ws,
                              size_t ws_bytes, hipStream_t st) {
@@ -2078,8 +2070,9 @@ int rg_mfma_upconv3_bwd_data(const void* gy, const float* w, void* gx, int N, in
   g.A = (const uint16_t*)gy; g.B = wt; g.C = gpad;
   g.M = Mp; g.Ncols = Cin; g.Cin = Cout; g.taps = 9;
   g.Hs = 2 * H; g.Ws = 2 * W; g.ldc = Cin; g.b_col = 9 * Cout; g.b_tap = Cout;
-  int rc = launch_gather2<MODE_C3T, EPI_BF16>("upconv3_bwd_data(mfma)", g, 1, g.M, (size_t)N * 4 * H * W * Cout * 2,
-                                              (size_t)Cout * 9 * Cin * 2, (char*)ws + gpb + wtb, ws_bytes - gpb - wtb, st);
+  int rc = launch_gather2<MODE_C3T, EPI_BF16>("upconv3_bwd_data(mfma)", g, gemm_plan(MODE_C3T, true, Mp, Cin, Cout, 9, Cin, (size_t)N * 4 * H * W * Cout * 2,
+                                                                                     (size_t)Cout * 9 * Cin * 2),
+                                              (char*)ws + gpb + wtb, ws_bytes - gpb - wtb, st);
   if (rc) return rc;
   hipLaunchKernelGGL(uppad_adjoint_bf16_kernel, dim3(grid_cap((size_t)N * H * W * (Cin >> 3))), dim3(256), 0, st, gpad,
                      (uint16_t*)gx, N, H, W, Cin);
@@ -2111,7 +2104,7 @@ static int upconv3_wgrad_split(int K, int Cout, int Cin) {
 }
 bool rg_mfma_upconv3_wgrad_supported(int N, int H, int W, int Cin, int Cout) {
   return Cout % 8 == 0 && Cin % 8 == 0 && rg_is_pow2(H) && rg_is_pow2(W) && !use_v1() &&
-         (size_t)N * 4 * H * W * Cout * 2 < 0x7fffff00ull && (size_t)N * (2 * H + 2) * (2 * W + 2) * Cin * 2 < 0x7fffff00ull;
+         fits_descriptor((size_t)N * 4 * H * W * Cout * 2) && fits_descriptor((size_t)N * (2 * H + 2) * (2 * W + 2) * Cin * 2);
 }
 size_t rg_mfma_upconv3_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout) {
   return rg_align_up((size_t)N * (2 * H + 2) * (2 * W + 2) * Cin * 2, 256) +

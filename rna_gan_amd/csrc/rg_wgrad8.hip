@@ -721,9 +721,15 @@ bool rg_wgrad8_supported(int K, int O, int I) {
   return O % 256 == 0 && (16 * I) % 256 == 0 && I % 8 == 0 && K >= 256;
 }
 
-// split-K plan: one block per CU when the tiles allow it (256 x 256 fp32 slabs are 256 KB per block and split)
-int rg_wgrad8_split(int K, int O, int I, int* kt_per_split) {
-  const int tiles = (O / 256) * (16 * I / 256);
+// The 128 x 512 form: O a multiple of 128 that the 256-row tile does not divide, 16 * I a multiple of 512.
+bool rg_wgrad8n_supported(int K, int O, int I) {
+  return O % 128 == 0 && O % 256 != 0 && (16 * I) % 512 == 0 && I % 8 == 0 && K >= 256;
+}
+
+// split-K plan of either form (bm x bn = 256 x 256 / 128 x 512): one block per CU when the tiles allow it (256 x 256 fp32 slabs
+// are 256 KB per block and split)
+int rg_wgrad8_split(int K, int O, int I, int bm, int bn, int* kt_per_split) {
+  const int tiles = (O / bm) * (16 * I / bn);
   const int nkt = (K + 63) / 64;
   const int target = rg_option("wgrad8_blocks", 256);
   int ns = (target + tiles - 1) / tiles;
@@ -731,24 +737,6 @@ int rg_wgrad8_split(int K, int O, int I, int* kt_per_split) {
   int per = (nkt + ns - 1) / ns;
   if (per < 4) per = 4;
   per = (per + 1) & ~1;                                   // even number of k-tiles per split (the loop is unrolled by two)
-  ns = (nkt + per - 1) / per;
-  *kt_per_split = per;
-  return ns;
-}
-
-// The 128 x 512 form: O a multiple of 128 that the 256-row tile does not divide, 16 * I a multiple of 512.
-bool rg_wgrad8n_supported(int K, int O, int I) {
-  return O % 128 == 0 && O % 256 != 0 && (16 * I) % 512 == 0 && I % 8 == 0 && K >= 256;
-}
-int rg_wgrad8n_split(int K, int O, int I, int* kt_per_split) {
-  const int tiles = (O / 128) * (16 * I / 512);
-  const int nkt = (K + 63) / 64;
-  const int target = rg_option("wgrad8_blocks", 256);
-  int ns = (target + tiles - 1) / tiles;
-  if (ns < 1) ns = 1;
-  int per = (nkt + ns - 1) / ns;
-  if (per < 4) per = 4;
-  per = (per + 1) & ~1;
   ns = (nkt + per - 1) / per;
   *kt_per_split = per;
   return ns;

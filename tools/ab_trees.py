@@ -9,6 +9,7 @@ against the working tree.  tools/ab_step.py is the in-process form for run-time 
 import argparse
 import json
 import os
+import statistics
 import subprocess
 import sys
 
@@ -17,6 +18,7 @@ ap.add_argument("--trees", required=True)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--json", default=None)
+ap.add_argument("--timeout", type=float, default=300, help="seconds one bench.py run may take")
 ap.add_argument("--cleanup", action="store_true",
                 help="afterwards remove every tree that lives under tools/scratch/ (extracted copies of other commits: they are not "
                      "source of this tree and inflate line counts / the gpurun snapshot)")
@@ -27,7 +29,8 @@ for r in range(a.rounds):
     for name, path in (trees if r % 2 == 0 else trees[::-1]):
         path = os.path.abspath(path)
         out = subprocess.run([sys.executable, os.path.join(path, "bench.py"), "--no-cpu-baseline", "--no-roofline", "--no-extras",
-                              "--steps", str(a.steps)], cwd=path, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+                              "--steps", str(a.steps)], cwd=path, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True,
+                             timeout=a.timeout)        # (a run that exceeds it raises: nothing more is started)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode != 0 or not line:
             print("[ab_trees] %s failed (rc %d)" % (name, out.returncode), file=sys.stderr)
@@ -39,6 +42,7 @@ summary = {"steps": a.steps, "rounds": a.rounds, "unit": "ms per iteration", "tr
 for n, p in trees:
     d = [x - y for x, y in zip(res[n], res[base])]
     summary["trees"].append({"name": n, "path": p, "ms": res[n], "mean": round(sum(res[n]) / len(res[n]), 3), "min": min(res[n]),
+                             "median": statistics.median(res[n]), "spread": round(max(res[n]) - min(res[n]), 3),
                              "delta_vs_first": {"mean": round(sum(d) / len(d), 3), "min": round(min(d), 3), "max": round(max(d), 3)}})
 line = json.dumps(summary)
 print(line)
