@@ -849,6 +849,24 @@ int rg_tile_transform(const void* src, int src_dtype, float* dst, int N, int C, 
 int rg_tile_gather_transform(const uint8_t* store, long long M, const int* index, float* dst, int N, int C, int S,
                              const int* codes, float mean, float stdv, void* stream);
 
+/* The batch of a RESIDENT expression table (rna_gan_amd.rna_tables; rna_gan_amd/csrc/rg_rows.hip): rows gathered by index into
+ * a dense, zero padded fp32 batch in one launch -- what the betaVAE training loop takes as "rna_data".
+ *   table [M][ld_table] fp32, of which columns [0, F) are read;  dst [N][ld_dst] fp32
+ *   index device array of N ints, or NULL = index[n] = n (then N <= M is required).  Repeated indices are allowed.
+ *   dst[n][c] = table[clamp(index[n], 0, M - 1)][c] for c < F, the bits unchanged;  dst[n][c] = 0 for F <= c < ld_dst.
+ * Every offset is computed in 64 bits (index ld_table passes 2^31 elements at about 112 000 rows of 19 198).  The kernel never
+ * reads outside table[0 .. M)[0 .. F): an index outside [0, M) is CLAMPED to the nearest valid row (negative -> 0, >= M ->
+ * M - 1).  That is a memory-safety guarantee, not an interface: callers validate their indices.  No workspace, no allocation, no
+ * host synchronisation; nothing outside dst[0 .. N)[0 .. ld_dst) is written; table and dst must not overlap.  Both buffers need
+ * 4-byte alignment only: per row the kernel takes the widest access the actual addresses of the source row and of the
+ * destination row allow (16-byte stores wherever a 16-byte-aligned chunk of the destination row lies inside it; 16-, 8- or
+ * 4-byte loads), the same bits on every path.  A plain kernel node: safe under graph capture, any stream.  N == 0: RG_OK,
+ * nothing launched.  RG_EINVAL (nothing launched) for a NULL table or dst, M <= 0 with N > 0, N < 0, F <= 0, ld_table < F,
+ * ld_dst < F, or index == NULL with N > M; RG_EUNSUPPORTED for more than 2^31 - 1 workgroups (N ceil((ld_dst + 6) / 4 / 1024)).
+ * No 16-bit type is involved: both builds behave identically. */
+int rg_rows_gather_f32(const float* table, long long M, int F, long long ld_table, const int* index, float* dst, int N,
+                       long long ld_dst, void* stream);
+
 /* The device-side tile export(rna_gan_amd.export; rna_gan_amd/csrc/rg_export.hip): generated images -> uint8 tiles, quantised and
  * laid out in one launch, so a batch leaves the device as C bytes per pixel instead of 4 C.
  *   src   [N][C][H][W] fp32;  dst N C H W bytes

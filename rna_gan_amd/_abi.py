@@ -146,6 +146,7 @@ PROTOTYPES = {
     "rg_u8_to_norm": (_i, [_p, _p, _z, _f, _f, _p]),
     "rg_tile_transform": (_i, [_p, _i, _p, _i, _i, _i, _p, _f, _f, _p]),
     "rg_tile_gather_transform": (_i, [_p, C.c_longlong, _p, _p, _i, _i, _i, _p, _f, _f, _p]),
+    "rg_rows_gather_f32": (_i, [_p, C.c_longlong, _i, C.c_longlong, _p, _p, _i, C.c_longlong, _p]),
     "rg_tile_export_u8": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _i, _p]),
     "rg_tile_qc_workspace_bytes": (_z, [_i, _i, _i]),
     "rg_tile_qc": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
@@ -208,7 +209,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES when an existing entry
-# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three, rg_tile_gather_transform) keeps the number -- load() refuses a library that lacks it
+# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three, rg_tile_gather_transform, rg_rows_gather_f32) keeps the number -- load() refuses a library that lacks it
 ABI_VERSION = 618
 
 _libs = {}
