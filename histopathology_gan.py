@@ -104,6 +104,14 @@ EXTRA_FLAGS = [
                              "generated tiles that the reference tiler's acceptance rule keeps -- a tissue mask over more than "
                              "20 % of the tile, not low-contrast (rna_gan_amd.tissue, on the device; no real tiles are judged); "
                              "with another metric over N samples it shares the noise (0 = off)"),
+    ("--cf_patients", int, 0, "--loss_type wganvae only: evaluate the conditioning fidelity "
+                              "(rna_gan_amd.metrics.ConditioningFidelity) after every epoch over the first P distinct RNA rows of "
+                              "the dataset: per patient, the mean features (--fd_extractor) of its real tiles and of --cf_tiles "
+                              "tiles generated from its row, then the rank of its own real centroid among the P for every "
+                              "generated one (0 = off, otherwise at least 2)"),
+    ("--cf_tiles", int, 8, "--cf_patients: tiles per patient -- generated, and at most that many readable real ones"),
+    ("--cf_report", str, "top1", "--cf_patients: which of top1, top5, mrr, median_rank is logged in metric_logs (all are kept per "
+                                 "epoch in the checkpointed metric's history)"),
     ("--device_transform", int, 0, "1 = the loader hands over uint8 tiles (a quarter of the host-to-device bytes) and one launch "
                                    "normalises them on the device, bit-identical to the host transform "
                                    "(rna_gan_amd.augment.InputTransform); 0 = the reference's host transform"),
@@ -172,6 +180,14 @@ def parse_args(argv=None):
         ap.error("--qc_samples must be 0 (off) or at least 2")
     if args.pr_report not in ("precision", "recall", "density", "coverage"):
         ap.error("--pr_report must be precision, recall, density or coverage")
+    if args.cf_patients < 0 or args.cf_patients == 1:
+        ap.error("--cf_patients must be 0 (off) or at least 2 (a rank among fewer than two patients says nothing)")
+    if args.cf_patients > 0 and args.loss_type != "wganvae":
+        ap.error("--cf_patients needs --loss_type wganvae (only that generator is conditioned on RNA)")
+    if args.cf_tiles < 1:
+        ap.error("--cf_tiles must be at least 1")
+    if args.cf_report not in ("top1", "top5", "mrr", "median_rank"):
+        ap.error("--cf_report must be top1, top5, mrr or median_rank")
     if args.device_transform not in (0, 1):
         ap.error("--device_transform must be 0 or 1")
     if args.augment not in ("none", "d4"):
@@ -269,6 +285,50 @@ def build_pr_metric(args, ds, losses, device, holder):
                          % (real.shape[0], args.pr_samples, args.pr_k, args.pr_k + 1))
     return PrecisionRecall(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch, nearest_k=args.pr_k,
                            report=args.pr_report)
+
+
+def build_cf_metric(args, ds, losses, device, holder):
+    """--cf_patients: the conditioning fidelity over the first P distinct RNA rows of ``ds`` -- distinct by the bytes of the fp32
+    row, the rule of DeviceTileSet.from_dataset -- each with its first --cf_tiles readable tiles (held on the device; uint8 under
+    --device_transform / --resident, normalised on the device as the training batches are).  The extractor is the shared one."""
+    from rna_gan_amd.metrics import ConditioningFidelity
+    if "extractor" not in holder:
+        from rna_gan_amd.fid import inception_features_device
+        holder["extractor"] = "discriminator" if args.fd_extractor == "discriminator" else \
+            inception_features_device(args.fd_extractor, device)
+    P_, T = args.cf_patients, args.cf_tiles
+    rows, row_index, tiles, patient_of, have = [], {}, [], [], []
+    known = getattr(ds, "rna_data_arrays", None)           # a PatchRNADataset: the rows without decoding a tile
+    for i in range(len(ds)):
+        if len(rows) == P_ and min(have) >= T:
+            break
+        item = None
+        row = known[i] if known is not None else None
+        if row is None:
+            item = ds[i]
+            row = item["rna_data"]
+        key = row.to(torch.float32).contiguous().numpy().tobytes()
+        p = row_index.get(key)
+        if p is None:
+            if len(rows) == P_:
+                continue
+            p = row_index[key] = len(rows)
+            rows.append(row.to(torch.float32))
+            have.append(0)
+        if have[p] >= T:
+            continue
+        image = (item if item is not None else ds[i])["image"]
+        if image is None:
+            continue
+        tiles.append(image)
+        patient_of.append(p)
+        have[p] += 1
+    if len(rows) < 2 or min(have) < 1:
+        raise SystemExit("--cf_patients: %d distinct RNA rows among %d items, %d of them without a readable tile"
+                         % (len(rows), len(ds), sum(1 for h in have if h < 1)))
+    return ConditioningFidelity(torch.stack(tiles).to(device), torch.tensor(patient_of, dtype=torch.int32), torch.stack(rows),
+                                losses[0].betavae, tiles_per_patient=T, extractor=holder["extractor"], seed=args.seed,
+                                batch_size=256, report=args.cf_report)
 
 
 def main():
@@ -377,6 +437,8 @@ def main():
             metrics.append(build_pr_metric(args, ds, losses, device, holder))
         if args.qc_samples > 0:
             metrics.append(build_qc_metric(args, ds, losses, device, holder))
+        if args.cf_patients > 0:
+            metrics.append(build_cf_metric(args, ds, losses, device, holder))
     metrics = metrics or None
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,

@@ -451,6 +451,43 @@ int rg_knn_radii2(const float* a, int lda, int n, int F, int k, void* ws, size_t
 int rg_radius_hits(const float* a, int lda, int na, const float* b, int ldb, int nb, int F, const double* rb2, void* ws,
                    size_t ws_bytes, int32_t* count, double* mind2, void* stream);
 
+/* The two primitives of the per-patient representations and the RNA-conditioning metric (rg_groupstat.hip;
+ * rna_gan_amd.representation, rna_gan_amd.metrics.ConditioningFidelity): fp64 sums of feature rows per GROUP (a patient's tiles)
+ * and the rank of every row's designated partner among the rows of another set of fp64 centroids.  No 16-bit type is involved:
+ * both builds behave identically.
+ * rg_group_sums_update: x is n rows of F fp32 features, row stride ldx >= F elements, any alignment; group is n int32 ids;
+ *   sums is [G][F] fp64 row-major and counts is [G] int64, both ACCUMULATED into:
+ *     sums[g][j]  += sum of (double)x[r][j] over the rows r < n with group[r] == g
+ *     counts[g]   += the number of such rows
+ *   The additions of an entry (g, j) form ONE chain in ascending r that starts from the value already in sums[g][j]; the one
+ *   thread that owns the entry walks the rows (group ids staged through LDS, only rows of its own group loaded): no atomics.
+ *   Consequences, relied upon: the result equals a sequential fp64 loop in row order bit for bit, for any floats, and it is the
+ *   same whether the rows arrive in one call or split over several calls at any boundary.
+ *   A row whose id is outside [0, G) is ignored: neither summed nor counted, its features are not read.  Only rows < n and
+ *   columns < F of x are read; nothing outside sums[G][F] and counts[G] is written; offsets into x and sums are computed in
+ *   64 bits.  No workspace, no allocation, no host synchronisation, safe under graph capture.  n == 0: RG_OK, nothing launched.
+ *   RG_EINVAL (nothing launched) for a NULL buffer, F < 1, G < 1, n < 0 or ldx < F; RG_EUNSUPPORTED for more than 2^31 - 1
+ *   workgroups (G ceil(F / 256)).
+ * rg_match_ranks: a is na rows and b is nb rows of F fp64 features, row strides lda / ldb >= F elements; target is na int32 row
+ *   indices of b, or NULL = target[r] = r (then na <= nb is required).  d2 is the squared distance of rg_knn_radii2 on fp64
+ *   operands: diff = a_f - b_f is one rounded subtraction, d2 = fma(diff, diff, d2) sequentially in ascending f from 0 (so the
+ *   value does not depend on tiling).  With t = target[r] and d* = d2(a_r, b_t), both outputs WRITTEN (not accumulated into):
+ *     dtarget[r] = d*
+ *     rank[r]    = #{ s != t : d2(a_r, b_s) < d* } + #{ s < t : d2(a_r, b_s) == d* }
+ *   Rank 0: the designated partner is the nearest row; ties are broken by index.  A NaN d2(a_r, b_s) never counts as closer; a
+ *   NaN d* gives rank[r] = nb - 1.  A target outside [0, nb) is CLAMPED (negative -> 0, >= nb -> nb - 1): a memory-safety
+ *   guarantee as in rg_rows_gather_f32, not an interface -- callers validate their targets.
+ *   A workgroup owns 64 rows of a and a share of the 64-row tiles of b; the counts are integers, summed with integer atomics
+ *   onto rank, which the call itself clears first (a memset node on the same stream) when the tiles of b are shared out: the
+ *   same bits on every run.  Rows past na / nb and columns past F are never read; nothing outside rank[na] and dtarget[na] is
+ *   written.  No workspace, no allocation, no host synchronisation, safe under graph capture.  na == 0: RG_OK, nothing written.
+ *   RG_EINVAL (nothing launched) for a NULL a, b, rank or dtarget, F < 1, nb < 1, na < 0, lda < F, ldb < F, or target == NULL
+ *   with na > nb. */
+int rg_group_sums_update(const float* x, int ldx, int n, int F, const int32_t* group, int G, double* sums, long long* counts,
+                         void* stream);
+int rg_match_ranks(const double* a, int lda, int na, const double* b, int ldb, int nb, int F, const int32_t* target, int32_t* rank,
+                   double* dtarget, void* stream);
+
 /* ---- split-K conv + train-mode BatchNorm without the intermediate passes (bf16 path) -------------------------------
  * The deep Conv2d / ConvTranspose2d layers at small batch run split-K (rg_conv_split(...) > 1): every launch leaves
  * nsplit fp32 slabs [nsplit][rows][C] in the workspace.  rg_conv_down_partial / rg_conv_up_partial run ONLY that launch

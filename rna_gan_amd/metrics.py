@@ -11,6 +11,9 @@ the device, an evaluation moves F + F^2 doubles per image set to the host and co
 (rg_polykernel_tile_sums), one double per 64 x 64 tile of row pairs to the host and no matrix function at all.
 ``PrecisionRecall`` separates what those two distances mix -- fidelity (precision, density) and diversity (recall, coverage) --
 by k-nearest-neighbour balls in the same feature space (rna_gan_amd.prdc: rg_knn_radii2, rg_radius_hits); four numbers come back.
+``ConditioningFidelity`` asks what none of those can, because they pool the generated set into one cloud: whether the tiles generated
+from patient p's expression row look like patient p -- per-patient centroids on the device (rna_gan_amd.representation:
+rg_group_sums_update) and the rank of each patient's own real centroid (rg_match_ranks).
 ``TissueYield`` judges the generated TILES, not features, and needs no real set: the fraction that the reference tiler's acceptance
 rule (rna_gan_amd.tissue: tissue mask coverage and contrast, rg_tile_qc) would keep -- the cheap signal for "the generator emits
 background".
@@ -396,3 +399,118 @@ class TissueYield(EvaluationMetric):
         self.last = self.calculate_score(stats)
         self.history.append(dict(self.last))
         return float(self.last["accepted"])
+
+
+class ConditioningFidelity(EvaluationMetric):
+    """Does the generator follow the expression row it is conditioned on?  Per patient, the mean features of its real tiles and of
+    ``tiles_per_patient`` tiles generated from its row (rna_gan_amd.representation: rg_group_sums_update on the device); every
+    generated centroid then ranks its own patient's real centroid among all P real centroids (rg_match_ranks).  A generator that
+    ignores its conditioning scores ``chance_top1`` = 1 / P whatever its tiles look like -- which FrechetDistance,
+    KernelDistance, PrecisionRecall and TissueYield, all pooling the generated set into one cloud, cannot tell.
+
+    real_tiles  (M, 3, S, S) tiles, uint8 or float normalised to [-1, 1]; kept where they are given.
+    patient_of  (M,) integers: tile m belongs to patient patient_of[m]; every patient needs at least one tile.
+    rna         (P >= 2, features) prepared expression rows, one per patient.
+    betavae     the frozen encoder of the ``wganvae`` losses (run in eval mode, its mode restored).
+    ``from_tile_set(ts, betavae, ...)`` takes the three tensors from a ``resident.DeviceTileSet`` with RNA.
+    tiles_per_patient  generated tiles per patient; the noise is ``representation.conditioned_noise(seed, group)``: a private
+                torch.Generator, the same values at every evaluation, the global generators never touched.
+    extractor   "discriminator" (the labelled proxy: the critic's trunk at native resolution; the real centroids are recomputed
+                at every call because the extractor moves with training) or a callable device-side extractor (images resized to
+                299 x 299 first; the real centroids are computed once and cached).
+    center      subtract each set's own grand mean before the distances (representation.match_ranks: the domain gap between
+                generated and real features is a common offset that would otherwise decide every rank).
+    report      which of "top1", "top5", "mrr", "median_rank" ``metric_ops`` returns; all scores of an evaluation are kept in
+                ``self.last`` and appended to ``self.history``, the ranks in ``self.last_rank``.
+    Both networks run in eval mode under no_grad and their modes are restored: a training run with the metric is bit-identical to
+    one without it.  Pickling keeps the settings and ``history`` only; ``set_data`` re-supplies tiles, ids, rows and encoder."""
+
+    REPORTS = ("top1", "top5", "mrr", "median_rank")
+
+    def __init__(self, real_tiles, patient_of, rna, betavae, tiles_per_patient=8, extractor="discriminator", seed=0,
+                 batch_size=256, center=True, report="top1", group=4096):
+        super().__init__()
+        if not (extractor == "discriminator" or callable(extractor)):
+            raise ValueError("extractor must be 'discriminator' or a callable device-side feature extractor")
+        if report not in self.REPORTS:
+            raise ValueError("report must be one of %s" % ", ".join(self.REPORTS))
+        self.extractor, self.report, self.center = extractor, report, bool(center)
+        self.tiles_per_patient, self.seed, self.batch_size, self.group = int(tiles_per_patient), int(seed), int(batch_size), int(group)
+        if self.tiles_per_patient < 1 or self.batch_size < 1 or self.group < 2:
+            raise ValueError("tiles_per_patient and batch_size must be >= 1 and group >= 2")
+        self.last, self.last_rank, self.history = None, None, []
+        self.set_data(real_tiles, patient_of, rna, betavae)
+
+    @classmethod
+    def from_tile_set(cls, ts, betavae, **kwargs):
+        if ts.rna is None:
+            raise ValueError("ConditioningFidelity needs a tile set with RNA rows")
+        return cls(ts.tiles, ts.row_of, ts.rna, betavae, **kwargs)
+
+    def set_data(self, real_tiles, patient_of, rna, betavae):
+        if not torch.is_tensor(real_tiles) or real_tiles.dim() != 4 or real_tiles.shape[1] != 3:
+            raise ValueError("real_tiles must be an (M, 3, S, S) tensor of tiles")
+        if real_tiles.dtype != torch.uint8 and not real_tiles.is_floating_point():
+            raise TypeError("real_tiles must be uint8 or float tiles")
+        if not torch.is_tensor(rna) or rna.dim() != 2 or rna.shape[0] < 2:
+            raise ValueError("rna must be (P >= 2, features): a rank among fewer than two patients says nothing")
+        patient_of = torch.as_tensor(patient_of)
+        P = int(rna.shape[0])
+        if patient_of.dim() != 1 or patient_of.shape[0] != real_tiles.shape[0] or patient_of.is_floating_point():
+            raise ValueError("patient_of must hold one integer per tile")
+        ids = patient_of.detach().cpu().long()
+        if ids.numel() == 0 or int(ids.min()) < 0 or int(ids.max()) >= P:
+            raise ValueError("patient_of points outside the %d rows of rna" % P)
+        if int((torch.bincount(ids, minlength=P) == 0).sum()):
+            raise ValueError("every patient needs at least one real tile")
+        self.real_tiles, self.patient_of, self.rna, self.betavae = real_tiles, patient_of.to(torch.int32), rna, betavae
+        self._real_centroids = None
+
+    def __getstate__(self):
+        return {"arg_map": dict(self.arg_map), "tiles_per_patient": self.tiles_per_patient, "seed": self.seed,
+                "batch_size": self.batch_size, "group": self.group, "center": self.center, "report": self.report,
+                "extractor": self.extractor if isinstance(self.extractor, str) else "callable",
+                "history": [dict(h) for h in self.history]}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.real_tiles = self.patient_of = self.rna = self.betavae = None
+        self._real_centroids = None
+        self.last, self.last_rank = None, None
+        self.history = [dict(h) for h in state.get("history", [])]
+
+    def calculate_score(self, fake_centroids, real_centroids=None):
+        from .representation import match_ranks, retrieval_scores
+        rank, _ = match_ranks(fake_centroids, real_centroids, None, self.center)
+        self.last_rank = rank
+        return retrieval_scores(rank, real_centroids.shape[0])
+
+    @torch.no_grad()
+    def metric_ops(self, generator, discriminator, device):
+        if self.real_tiles is None:
+            raise RuntimeError("ConditioningFidelity: no data (an unpickled metric keeps its settings only: call set_data)")
+        from . import fid as FID
+        from .representation import patient_representations
+        modes = [(m, m.training) for m in (generator, discriminator)]
+        try:
+            for m, _ in modes:
+                m.eval()
+            if self.extractor == "discriminator":
+                extract, resize = FID.discriminator_features_device(discriminator), None
+            else:
+                extract, resize = self.extractor, 299
+            real = self._real_centroids
+            reps = patient_representations(extract, real=(self.real_tiles, self.patient_of) if real is None else None,
+                                           conditioned=generator, betavae=self.betavae, gene_exp=self.rna,
+                                           tiles_per_patient=self.tiles_per_patient, n_patients=self.rna.shape[0], seed=self.seed,
+                                           batch_size=self.batch_size, group=self.group, resize=resize)
+            if real is None:
+                real = reps["real"]
+                if resize is not None:                       # a fixed extractor: the real centroids never change
+                    self._real_centroids = real
+            self.last = self.calculate_score(reps["conditioned"], real)
+            self.history.append(dict(self.last))
+            return float(self.last[self.report])
+        finally:
+            for m, was in modes:
+                m.train(was)
