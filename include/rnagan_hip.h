@@ -999,6 +999,71 @@ int rg_window_resize_u8(const uint8_t* raster, int RH, int RW, const int32_t* or
 int rg_mask_erode(const uint8_t* mask, uint8_t* out, int N, int H, int W, int radius, void* stream);
 int rg_box_reduce_u8(const uint8_t* raster, int RH, int RW, int factor, uint8_t* out, void* stream);
 
+/* Macenko stain normalisation of uint8 RGB tiles (rna_gan_amd.stain; rna_gan_amd/csrc/rg_stain.hip): the method of Macenko et al.
+ * (2009) restated on fixed-point tables that the HOST builds in fp64 with rint, so that everything the device computes is an
+ * INTEGER and every count, sum and byte is exact.  The fit of a set of tiles is three statistics passes with a little host
+ * arithmetic between them; a fourth pass applies it.  tests/stain_refs.py restates all of it in numpy.
+ *
+ * Constants (rna_gan_amd.stain): IO 240 the white level; BETA 0.15 the stained-pixel floor on the optical density; ALPHA 1 the angle
+ *   percentile; QOD 12 fixed-point bits of the optical density; QV 14 of the plane basis and the bin directions; K 1024 angle bins;
+ *   QP 20 bits of the pseudo-inverse; CB 4096 concentration bins of width 2^CSH = 2^3 in Q12; QS 16, QH 14, QO 8 bits of the scale,
+ *   the target stain matrix and the output optical density.
+ * Conventions: every sum and product is exact in int64; >> is the arithmetic (floor) shift.
+ * Host tables:
+ *   od_lut[v] = rint(-ln((v + 1) / IO) 2^QOD), int32 [256]; negative for v >= IO, not clamped.  |od_lut[v]| <= 23170 is part of the
+ *               contract (four squares then sum below 2^31): the table above reaches 22449.  beta_q = rint(BETA 2^QOD) = 614.
+ *   dirs        int32 [K - 1][2]: for k = 1 .. K - 1, theta_k = -pi/2 + k pi / K, (rint(cos theta_k 2^QV), rint(sin theta_k 2^QV)).
+ *   out_lut[j] = clip(rint(IO exp(-(j - OFF) / 2^QO)), 0, 255), uint8 [L]; OFF the smallest offset at which index 0 gives 255 (16),
+ *               L the smallest length whose last entry is 0.
+ * A pixel's optical density is od = od_lut[(R, G, B)]; it is STAINED when od_R, od_G and od_B are all >= beta_q.
+ *   tiles  N tiles of H x W pixels, 3 channels, uint8, any alignment.  flags: RG_EXPORT_PLANAR clear: [N][H][W][3], set:
+ *          [N][3][H][W]; RG_EXPORT_REVERSE: the stored channel order is B, G, R.  No other bit.
+ *
+ * rg_stain_moments     out int64 [10], over the stained pixels: the count, sum od_c (R, G, B), sum od_c od_d for (c, d) = RR, RG, RB,
+ *                      GG, GB, BB.  Host: covariance (n S2 - S1 S1^T) / (n (n - 1)) / 2^(2 QOD), the numerator in exact integers;
+ *                      numpy.linalg.eigh; the two leading eigenvectors e1, e2, each negated if its component sum is negative.
+ * rg_stain_angle_hist  basis6: SIX HOST ints Eq1[3], Eq2[3] = rint(e 2^QV), each within +-30000.  Per stained pixel
+ *                      p1 = sum od_c Eq1_c, p2 = sum od_c Eq2_c.  p1 <= 0: counted in hist[K] alone (outside).  Otherwise
+ *                      bin = #{k in 1 .. K - 1 : cos_k p2 - sin_k p1 >= 0}, in 0 .. K - 1; the predicate is monotone in k for p1 > 0
+ *                      (the quantised directions are strictly ordered by angle and have cos_k > 0), so the kernel finds the count by
+ *                      binary search.  hist uint64 [K + 1].  2 <= K <= 2048.
+ *                      Host: the percentile q (an integer) of a histogram is the first bin whose cumulative count exceeds
+ *                      (q (total - 1)) / 100 (integer division), taken at the bin centre: phi = -pi/2 + (bin + 0.5) pi / K.
+ *                      v = e1 cos phi + e2 sin phi for phi_ALPHA and phi_(100 - ALPHA); the column with the larger R component is
+ *                      haematoxylin: HE (3 x 2).  Pq = rint(pinv(HE) 2^QP).
+ * rg_stain_conc_hist   over ALL pixels: pinv6 SIX HOST long long Pq[stain][channel], each within +-2^40;
+ *                      conc_s = (sum_c Pq[s][c] od_c) >> qp (Q12 for qp = QP); bin = clamp(conc_s >> csh, 0, bins - 1).
+ *                      hist uint64 [2][bins].  1 <= bins <= 4096, 0 <= qp <= 40, 0 <= csh <= 31.
+ *                      Host: max_conc_s = the centre of the 99th-percentile bin, (bin + 0.5) 2^CSH / 2^QOD.
+ * rg_stain_apply       src -> dst, the same layout and channel order.  scale2: TWO HOST long long scale_q = rint(max_t / max_conc 2^QS)
+ *                      >= 0; href6: SIX HOST ints Hq[channel][stain] = rint(HE_t 2^QH) of the target; shift = QH + QOD - QO.
+ *                        conc2_s = (conc_s scale_q_s) >> qs
+ *                        od2_c = (sum_s Hq[c][s] conc2_s + 2^(shift - 1)) >> shift          (no rounding term for shift == 0)
+ *                        byte_c = out_lut[clamp(od2_c + off, 0, L - 1)]
+ *                      One pass; dst == src is the in-place call, otherwise dst must not overlap src.  A lane takes four pixels
+ *                      with dword loads and stores where src and dst are 4-byte aligned (planar: and H W % 4 == 0), single bytes
+ *                      otherwise: the same bytes either way.  1 <= L <= 8192, 0 <= off < L, qp, qs, shift in 0 .. 40; operands so
+ *                      large that a sum of the contract would leave int64 are refused.
+ * accumulate == 0: the call zeroes its output first (a small kernel in front of the counting one); != 0: it adds to what is there, so a
+ * set that arrives in batches gets the same integers in any order.  Device tables are staged in LDS; counting is integer LDS
+ * atomics, then one 64-bit global integer atomic per occupied bin per workgroup: no floating-point atomics, so no result depends on
+ * the launch plan.  Each entry point is one kernel launch (plus that zeroing one) on `stream`: no host synchronisation, no allocation,
+ * safe under graph capture.  Only the stated buffers are read or written; a device table that is not the contract's gives other
+ * numbers, never an access outside them.  N == 0: RG_OK, nothing launched and nothing zeroed.  RG_EINVAL (nothing launched) for a
+ * NULL buffer, N < 0, H or W <= 0, an unknown flag bit, K, bins, L, off or a shift out of range, a host operand out of range, od_lut
+ * or dirs not 4-byte aligned, out or hist not 8-byte aligned, dst partly overlapping src; RG_EUNSUPPORTED for more than 2^33
+ * pixels per call (up to there sum od^2 stays exact in int64) or more than 2^31 - 1 workgroups.  No 16-bit type is involved: both
+ * builds behave identically. */
+int rg_stain_moments(const uint8_t* tiles, int N, int H, int W, int flags, const int32_t* od_lut, int beta_q, int64_t* out,
+                     int accumulate, void* stream);
+int rg_stain_angle_hist(const uint8_t* tiles, int N, int H, int W, int flags, const int32_t* od_lut, int beta_q, const int* basis6,
+                        const int32_t* dirs, int K, uint64_t* hist, int accumulate, void* stream);
+int rg_stain_conc_hist(const uint8_t* tiles, int N, int H, int W, int flags, const int32_t* od_lut, const long long* pinv6, int qp,
+                       int csh, int bins, uint64_t* hist, int accumulate, void* stream);
+int rg_stain_apply(const uint8_t* src, uint8_t* dst, int N, int H, int W, int flags, const int32_t* od_lut, const long long* pinv6,
+                   int qp, const long long* scale2, int qs, const int* href6, int shift, const uint8_t* out_lut, int L, int off,
+                   void* stream);
+
 /* ---- the fp32 mode on the bf16 matrix cores, operands split ONCE PER TENSOR (rna_gan_amd/csrc/rg_conv8f.hip, rg_wgrad8f.hip) ----
  * The reference computes in fp32 (src/betaVAE.py:184,223; the GAN CLI never enables AMP).  An fp32 value is the exact sum of three
  * bf16 numbers v = h + m + l; rg_split_planes writes them as a plane-major buffer planes[3][n] (bf16, n % 8 == 0) in one

@@ -21,6 +21,12 @@ Per slide (its id is the file name up to its second dot, as in the reference):
                               the slide named <id> (--out_format store, the only format).
                               A slide whose --patch_path/<id> exists is SKIPPED, as in the reference.
   --qc_report                 also writes --patch_path/<id>/qc.csv: origin and acceptance statistics of every stored tile.
+  --stain_norm macenko        the slide's accepted tiles are fitted together as one set (rna_gan_amd.stain: Macenko's method on
+                              integer tables) and normalised on the device to --stain_target (``reference``, or a JSON file: a
+                              StainFit, or the stain.json of an earlier run -- a cohort can be normalised to one of its own slides)
+                              before they are stored; --patch_path/<id>/stain.json holds the fit and the target.  Acceptance and
+                              qc.csv keep judging the raw windows.  A slide that cannot be fitted is stored unnormalised, with a
+                              message and "normalized": false in stain.json.  Default none: every byte as before.
 --synthetic tiles --synthetic_slides seeded rasters of --synthetic_size (rna_gan_amd.tiler.synthetic_slide) named
 synthetic_<k>.svs instead of reading --wsi_path.  --num_process is accepted for the reference's command lines and ignored: one
 process drives one device.
@@ -53,6 +59,8 @@ EXTRA_FLAGS = [
     ("--synthetic_size", str, "2048x2560", "--synthetic: rows x columns of each raster"),
     ("--seed", int, 0, "--synthetic: seed of the first raster"),
     ("--device", int, 0, "device index"),
+    ("--stain_norm", str, "none", "none, or macenko: fit each slide's accepted tiles together and normalise them on the device"),
+    ("--stain_target", str, "reference", "reference (the published Macenko target), or a JSON file holding a StainFit or an earlier run's stain.json"),
 ]
 IMAGE_SUFFIXES = (".png", ".tif", ".tiff", ".jpg", ".jpeg", ".bmp")
 QC_COLUMNS = ("slide", "tile", "x", "y", "otsu_r", "otsu_g", "otsu_b", "otsu_s", "tissue_fraction", "luma_p1", "luma_p99")
@@ -81,6 +89,12 @@ def parse_args(argv=None):
         ap.error("--min_tissue must be in [0, 1]")
     if args.out_format != "store":
         ap.error("--out_format must be store")
+    if args.stain_norm not in ("none", "macenko"):
+        ap.error("--stain_norm must be none or macenko")
+    if args.stain_target != "reference" and args.stain_norm == "none":
+        ap.error("--stain_target needs --stain_norm macenko")
+    if args.stain_target != "reference" and not os.path.isfile(args.stain_target):
+        ap.error("--stain_target must be reference or an existing JSON file")
     try:
         rows, cols = (int(v) for v in args.synthetic_size.lower().split("x"))
         if rows < 1 or cols < 1:
@@ -154,6 +168,9 @@ def run(args):
     device = torch.device("cuda", args.device)
     torch.cuda.set_device(device)
     written = []
+    if args.stain_norm == "macenko":
+        from rna_gan_amd import stain
+        target = stain.load_target(args.stain_target)
     for sid, src, mag in list_slides(args):
         folder = os.path.join(args.patch_path, sid)
         if os.path.isdir(folder):
@@ -181,7 +198,20 @@ def run(args):
             os.makedirs(os.path.dirname(mask_file), exist_ok=True)
             np.save(mask_file, res.mask.cpu().numpy().astype(bool))
             written.append(mask_file)
-        tiles = res.tiles.cpu().numpy()
+        tiles = res.tiles
+        if args.stain_norm == "macenko":                 # the acceptance rule and qc.csv have judged the raw windows
+            fitted, message = None, None
+            try:
+                fitted = stain.fit(tiles, layout="nhwc", order="rgb", batch=args.batch)
+                tiles = stain.normalize(tiles, fitted, target)
+            except stain.StainFitError as e:
+                message = str(e)
+                print("slide %s: not stain-normalised, stored as tiled: %s" % (sid, message))
+            path = os.path.join(folder, "stain.json")
+            with open(path, "w") as f:
+                f.write(stain.stain_report(fitted, target, message is None, message))
+            written.append(path)
+        tiles = tiles.cpu().numpy()
         path = os.path.join(folder, sid.replace(".svs", ".db"))
         write_tile_store(path, tiles, slide_id=sid, stored=True, channel_order="rgb")
         written.append(path)
