@@ -12,7 +12,8 @@ preparation; slide databases as LMDB files when the ``lmdb`` package is installe
 ``--synthetic`` trains on synthetic tiles / RNA rows of the right shapes (what bench.py measures).  Extra flags: --batch_size (reference hard-codes 8),
 --precision, --betavae_checkpoint, --steps_per_epoch; --device_transform 1 hands the uint8 tiles to the device and normalises
 them there, --augment d4 applies one of the eight symmetries of the square per real sample (rna_gan_amd.augment);
---resident 1 keeps the rank's training tiles on the device as uint8 and forms every batch there (rna_gan_amd.resident).
+--resident 1 keeps the rank's training tiles on the device as uint8 and forms every batch there (rna_gan_amd.resident); with it, --mem_samples N audits N generated tiles per epoch for memorised
+training tiles (rna_gan_amd.metrics.Memorisation; data parallel: against the rank's own shard).
 """
 import argparse
 import datetime
@@ -124,6 +125,13 @@ EXTRA_FLAGS = [
                            "are dropped once, every batch is full; the set must fit the device (--resident_max_gb)"),
     ("--resident_max_gb", float, 0.0, "--resident 1: the memory budget of the set in GiB (0 = the device's free memory minus "
                                       "8 GiB); a set that needs more is refused before anything is uploaded"),
+    ("--mem_samples", int, 0, "--resident 1 only: audit memorisation (rna_gan_amd.metrics.Memorisation) after every epoch: the "
+                              "exact nearest training tiles of N generated tiles among the rank's resident set, by int8 "
+                              "block-mean descriptors on the device (rna_gan_amd.nearest); logs the fraction of samples that are "
+                              "closer to a training tile than any other training tile is (0 = off)"),
+    ("--mem_factor", int, 4, "--mem_samples: the descriptor averages the tile over blocks of this size (1, 2, 4, 8, 16 or 32)"),
+    ("--mem_d4", int, 1, "--mem_samples: 1 = search every sample under all eight symmetries of the square (what --augment d4 "
+                         "can teach the generator to return), 0 = as generated"),
 ]
 
 
@@ -196,6 +204,14 @@ def parse_args(argv=None):
         ap.error("--resident must be 0 or 1")
     if args.resident_max_gb < 0:
         ap.error("--resident_max_gb must be >= 0")
+    if args.mem_samples < 0:
+        ap.error("--mem_samples must be >= 0")
+    if args.mem_samples > 0 and not args.resident:
+        ap.error("--mem_samples needs --resident 1: the audit searches the training tiles where they are kept on the device")
+    if args.mem_factor not in (1, 2, 4, 8, 16, 32):
+        ap.error("--mem_factor must be 1, 2, 4, 8, 16 or 32")
+    if args.mem_d4 not in (0, 1):
+        ap.error("--mem_d4 must be 0 or 1")
     return args
 
 
@@ -273,6 +289,16 @@ def build_qc_metric(args, ds, losses, device, holder):
     from rna_gan_amd.metrics import TissueYield
     real, _extractor, noise, batch = metric_inputs(args, args.qc_samples, "--qc_samples", ds, losses, device, holder)
     return TissueYield(int(real.shape[0]), noise=noise, seed=args.seed, batch_size=batch)
+
+
+def build_mem_metric(args, ds, losses, device, holder):
+    """--mem_samples: the memorisation audit of N generated tiles.  Built without training tiles -- the resident set does not exist
+    yet; main() hands it over with ``set_train`` -- and with metric_inputs' noise, as the tissue yield (wganvae: from the RNA rows of
+    the first N items, shared with the other metrics over N samples)."""
+    from rna_gan_amd.metrics import Memorisation
+    real, _extractor, noise, batch = metric_inputs(args, args.mem_samples, "--mem_samples", ds, losses, device, holder)
+    return Memorisation(None, int(real.shape[0]), factor=args.mem_factor, d4=bool(args.mem_d4), noise=noise, seed=args.seed,
+                        batch_size=batch)
 
 
 def build_pr_metric(args, ds, losses, device, holder):
@@ -439,6 +465,8 @@ def main():
             metrics.append(build_qc_metric(args, ds, losses, device, holder))
         if args.cf_patients > 0:
             metrics.append(build_cf_metric(args, ds, losses, device, holder))
+        if args.mem_samples > 0:
+            metrics.append(build_mem_metric(args, ds, losses, device, holder))
     metrics = metrics or None
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,
@@ -456,6 +484,9 @@ def main():
         loader = DeviceTileLoader(tiles, args.batch_size, transform=input_transform, seed=args.seed, rank=D_.rank())
         if len(loader) == 0:
             raise SystemExit("--resident 1: %d readable tiles do not fill one batch of %d" % (len(tiles), args.batch_size))
+        for metric in metrics or []:
+            if hasattr(metric, "set_train"):              # --mem_samples: the audit searches the rank's resident tiles
+                metric.set_train(tiles)
     if args.checkpoint is not None:
         trainer.load_model(load_path=args.checkpoint)
     for loss in losses:                                   # identical frozen encoders on every rank (rank 0's)

@@ -1064,6 +1064,49 @@ int rg_stain_apply(const uint8_t* src, uint8_t* dst, int N, int H, int W, int fl
                    int qp, const long long* scale2, int qs, const int* href6, int shift, const uint8_t* out_lut, int L, int off,
                    void* stream);
 
+/* ---- memorisation audit: int8 tile descriptors and their exact nearest neighbours (rna_gan_amd/csrc/rg_nn.hip) ----
+ * rna_gan_amd.nearest asks which training tiles a generated tile is closest to.  Tiles are compared through DESCRIPTORS: the tile
+ * averaged over f x f blocks, recentred to int8.  Every quantity is an integer and is computed exactly; tests/nn_audit_refs.py
+ * restates both entry points in numpy.
+ *
+ * rg_tile_descriptor_i8   tiles uint8 [N][C][S][S] -> desc int8 [N][ldd], norm2 int32 [N].  P = S / f, D = C P P:
+ *                           desc[n][c P P + y P + x] = (sum of the f x f block (y, x) of channel c + f f / 2) / (f f) - 128
+ *                         (integer division: round half up; bytes 0 and 255 give -128 and 127), columns D .. ldd - 1 = 0,
+ *                         norm2[n] = sum_j desc[n][j]^2.  f in {1, 2, 4, 8, 16, 32}, S % f == 0, ldd % 64 == 0, ldd >= D.
+ *                         D <= 32 768, else RG_EUNSUPPORTED: then D 255^2 < 2^31 and every norm, dot product and squared distance
+ *                         fits int32.  One launch of N workgroups (a workgroup owns a tile, so norm2 is one block reduction); 16-byte
+ *                         loads where S % 16 == 0, f <= 16 and tiles and desc are 16-byte aligned, single bytes otherwise: the same
+ *                         integers.  No workspace.  N == 0: RG_OK, nothing launched.  RG_EINVAL (nothing launched) for a NULL
+ *                         buffer, N < 0, C or S <= 0, a bad f, S % f != 0, a bad ldd, norm2 not 4-byte aligned, or desc / norm2
+ *                         overlapping tiles or each other.  Only desc[N][ldd] and norm2[N] are written, only tiles is read.
+ * rg_nn_topk_i8           a int8 [Q][ldd] with norms na2 int32 [Q], b int8 [N][ldd] with nb2 int32 [N]; columns 0 .. D - 1 of a row
+ *                         are its descriptor (D % 64 == 0, D <= 32 768, ldd >= D, ldd % 16 == 0); columns beyond D are not read.
+ *                           d2(q, r) = na2[q] + nb2[r] - 2 <a_q, b_r>          (int32; formed modulo 2^32 and read as unsigned, which
+ *                                                                               is the distance itself when the norms are the rows')
+ *                           key(q, r) = ((uint64) d2(q, r) << 32) | r
+ *                         keys uint64 [Q][k] receives, ascending, the k smallest keys of query q over the candidate rows r: all of
+ *                         [0, N) except exclude[q] (exclude: NULL, or int32 [Q]; a value outside [0, N) excludes nothing).  The
+ *                         keys are one total order -- ties in d2 go to the lower row -- so the result depends neither on the tiling
+ *                         nor on the sharing rule below nor on the run.  1 <= k <= 8.  The dot products are
+ *                         v_mfma_i32_16x16x64_i8; no floating-point instruction, no atomic.
+ *                         SHARING RULE: a workgroup owns 128 queries and walks consecutive 128-row tiles of b.  With
+ *                         tiles = ceil(N / 128) and q_blocks = ceil(Q / 128), the tiles of a query block are cut into shares of
+ *                         ceil(tiles / max(1, 1024 / q_blocks)) consecutive tiles, one workgroup each (Q <= 128: N > 128 already
+ *                         gives two shares); each share's 8 best keys per query go to ws as [share][8][Q] and a second kernel, one
+ *                         thread per query, merges them.  rg_nn_topk_ws_bytes(Q, N, k) is that size.  ws contents are irrelevant
+ *                         before and after the call.  Two launches on `stream`; no host synchronisation, no allocation, safe under
+ *                         graph capture.  Q == 0: RG_OK, nothing launched.
+ *                         Fewer than k candidates is RG_EINVAL.  The host does not read exclude, so with exclude != NULL one row
+ *                         counts as excluded whatever its values are: N - 1 >= k is required then, N >= k otherwise.
+ *                         RG_EINVAL (nothing launched) also for a NULL a, na2, b, nb2 or keys, Q or N < 0, a bad D, ldd or k, a or b
+ *                         not 16-byte, an int32 operand not 4-byte, keys or ws not 8-byte aligned; RG_EWORKSPACE for a NULL or short
+ *                         workspace; RG_EUNSUPPORTED for D > 32 768 or more than 2^31 - 1 workgroups.
+ * No 16-bit type is involved: both builds behave identically. */
+int rg_tile_descriptor_i8(const uint8_t* tiles, int N, int C, int S, int f, int8_t* desc, long long ldd, int32_t* norm2, void* stream);
+size_t rg_nn_topk_ws_bytes(int Q, long long N, int k);
+int rg_nn_topk_i8(const int8_t* a, const int32_t* na2, int Q, const int8_t* b, const int32_t* nb2, long long N, int D, long long ldd,
+                  int k, const int32_t* exclude, uint64_t* keys, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the fp32 mode on the bf16 matrix cores, operands split ONCE PER TENSOR (rna_gan_amd/csrc/rg_conv8f.hip, rg_wgrad8f.hip) ----
  * The reference computes in fp32 (src/betaVAE.py:184,223; the GAN CLI never enables AMP).  An fp32 value is the exact sum of three
  * bf16 numbers v = h + m + l; rg_split_planes writes them as a plane-major buffer planes[3][n] (bf16, n % 8 == 0) in one

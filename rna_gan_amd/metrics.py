@@ -17,6 +17,9 @@ rg_group_sums_update) and the rank of each patient's own real centroid (rg_match
 ``TissueYield`` judges the generated TILES, not features, and needs no real set: the fraction that the reference tiler's acceptance
 rule (rna_gan_amd.tissue: tissue mask coverage and contrast, rg_tile_qc) would keep -- the cheap signal for "the generator emits
 background".
+``Memorisation`` asks the question all of the above answer the wrong way round -- a generator that copies its training tiles
+scores BETTER on each of them: the exact nearest training tiles of the generated tiles (rna_gan_amd.nearest: rg_tile_descriptor_i8,
+rg_nn_topk_i8) and the fraction that is closer to one than any other training tile is.
 """
 from __future__ import annotations
 
@@ -514,3 +517,98 @@ class ConditioningFidelity(EvaluationMetric):
         finally:
             for m, was in modes:
                 m.train(was)
+
+
+class Memorisation(EvaluationMetric):
+    """Is the generator reproducing its training tiles?  The one failure every metric above REWARDS: a memorised tile is perfect in
+    fidelity, covers its real neighbour and follows its patient's expression row.  ``samples`` generated tiles go through
+    ``synthesize`` -> ``export.tiles_u8(layout="nchw")`` and are searched against the int8 block-mean descriptors of the training
+    tiles (rna_gan_amd.nearest: rg_tile_descriptor_i8, rg_nn_topk_i8 on the integer matrix cores -- exact integers); a sample counts
+    as copied when it is closer to its nearest training tile than any OTHER training tile is (Alaa et al. 2022).  Samples of the
+    training distribution itself are flagged about half of the time, so ``copy_rate`` near 0.5 is what a generator that does not
+    memorise converges to; copying pushes it towards 1 (nearest.audit).
+
+    train_tiles  (M, C, S, S) uint8 tiles, kept where they are given (``from_tile_set(ts, ...)``: a resident.DeviceTileSet's), or
+                 None until ``set_train``.  The descriptor index is built on first use and kept.
+    factor       the descriptor's block size (nearest.FACTORS);  k: neighbours kept per sample (``self.last_result``).
+    d4           search every sample under all eight symmetries of the square (training under augment="d4").
+    heldout      real uint8 tiles the generator never saw: adds ``closer_than_heldout`` (Meehan et al. 2020).
+    noise, seed, batch_size, encoding_dims: as TissueYield; the generator runs in eval mode under no_grad, its mode is restored.
+    ``metric_ops`` returns ``copy_rate`` (what the trainer logs); ``self.last`` and, per evaluation, ``self.history`` keep
+    {"copy_rate", "exact", "min_d2", "median_d2"} and "closer_than_heldout" when held-out tiles were given.  An exact duplicate pair
+    inside the training set has loo_d2 = 0: a copy of either is never ``copied`` and shows in "exact" (nearest.audit).
+    Data parallel: the metric audits against the tiles it was given -- with ``from_tile_set`` the RANK'S OWN SHARD, as
+    ConditioningFidelity.from_tile_set does; there is no index across ranks, so a copy of another rank's tile is not seen.
+    Pickling keeps the settings and ``history``; tiles, index and noise are never pickled (``set_train`` re-supplies the tiles)."""
+
+    def __init__(self, train_tiles, samples, factor=4, k=1, d4=False, heldout=None, noise=None, seed=0, batch_size=256,
+                 encoding_dims=None):
+        super().__init__()
+        from .nearest import FACTORS, K_MAX
+        self.n_fake = int(samples)
+        if self.n_fake < 1:
+            raise ValueError("samples must be >= 1")
+        self.factor, self.k, self.d4 = int(factor), int(k), bool(d4)
+        if self.factor not in FACTORS or not 1 <= self.k <= K_MAX:
+            raise ValueError("factor must be one of %s and k in 1..%d" % (FACTORS, K_MAX))
+        self.seed = int(seed)
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self._rng = torch.Generator().manual_seed(self.seed)
+        if torch.is_tensor(noise) and noise.shape[0] != self.n_fake:
+            raise ValueError("noise has %d rows, samples is %d" % (noise.shape[0], self.n_fake))
+        self.noise = noise
+        if noise is None and encoding_dims is not None:
+            self.noise = torch.randn(self.n_fake, int(encoding_dims), generator=self._rng)
+        self.last, self.last_result, self.history = None, None, []
+        self.train_tiles = self.heldout = self._index = None
+        self.set_train(train_tiles, heldout)
+
+    @classmethod
+    def from_tile_set(cls, ts, samples, **kwargs):
+        return cls(ts.tiles, samples, **kwargs)
+
+    _noise_for = _GeneratedAgainstReal._noise_for
+    _fake_batches = _GeneratedAgainstReal._fake_batches
+
+    def set_train(self, train_tiles, heldout=None):
+        train_tiles = getattr(train_tiles, "tiles", train_tiles)
+        for t in (train_tiles, heldout):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 4):
+                raise ValueError("training and held-out tiles are (M, C, S, S) uint8 tensors")
+        self.train_tiles, self.heldout, self._index = train_tiles, heldout, None
+
+    def __getstate__(self):
+        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
+                "factor": self.factor, "k": self.k, "d4": self.d4, "history": [dict(h) for h in self.history]}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.noise = None
+        self.train_tiles = self.heldout = self._index = None
+        self.last, self.last_result = None, None
+        self.history = [dict(h) for h in state.get("history", [])]
+        self._rng = torch.Generator().manual_seed(self.seed)
+
+    def preprocess(self, x):
+        """fp32 [-1, 1] NCHW images -> planar uint8 tiles (the bytes a store would hold, the training set's layout), on the device."""
+        from .export import tiles_u8
+        return tiles_u8(x.float().contiguous(), layout="nchw")
+
+    def calculate_score(self, generated_u8):
+        from .nearest import TrainIndex, audit
+        if self._index is None:
+            self._index = TrainIndex(self.train_tiles, factor=self.factor)
+        heldout = None if self.heldout is None else self.heldout.to(self._index.device)
+        self.last_result = audit(generated_u8.to(self._index.device), self._index, k=self.k, d4=self.d4, heldout_u8=heldout)
+        return self.last_result.summary()
+
+    generated_tiles = TissueYield.generated_tiles
+
+    def metric_ops(self, generator, device):
+        if self.train_tiles is None:
+            raise RuntimeError("Memorisation: no training tiles (an unpickled metric keeps its settings only: call set_train)")
+        self.last = self.calculate_score(torch.cat(self.generated_tiles(generator, device)))
+        self.history.append(dict(self.last))
+        return float(self.last["copy_rate"])
