@@ -3,7 +3,7 @@
 // features' first and second raw moments.  With them an evaluation moves F + F^2 doubles to the host and nothing else.
 // And the one kernel of the kernel distance (rna_gan_amd.kid): fp64 sums of a polynomial kernel over 64 x 64 tiles of row pairs.
 // Nothing here depends on the build's 16-bit storage type: both builds compile the same code.
-#include "rg_internal.h"
+#include "rg_pairtile.h"
 
 namespace {
 
@@ -70,15 +70,15 @@ __global__ __launch_bounds__(256) void resize_bilinear01_kernel(const S* __restr
 // instruction buys no rate, and a 4 x 4 register tile per thread (16 FMAs for two 16-byte LDS reads and 8 conversions) keeps
 // the vector pipe fed without its non-standard C/D lane map.
 constexpr int MT = 64;            // tile edge: 16 x 16 threads, 4 x 4 results each
+static_assert(MT == PAIR_ROWS, "rg_moments_update counts its column tiles with pair_tiles");
 constexpr int MK = 32;            // rows of x staged per pass
 
 __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ x, int ldx, int n, int F, double* __restrict__ s1,
                                                       double* __restrict__ s2, int T) {
   __shared__ __attribute__((aligned(16))) float xi[MK][MT];
   __shared__ __attribute__((aligned(16))) float xj[MK][MT];
-  int ti = 0, rem = (int)blockIdx.x;                        // linear index -> (ti, tj) of the upper triangle, row by row
-  while (rem >= T - ti) { rem -= T - ti; ++ti; }
-  const int tj = ti + rem;
+  int ti, tj;
+  upper_triangle_tile((int)blockIdx.x, T, ti, tj);
   const bool diag = ti == tj;
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int i0 = ti * MT, j0 = tj * MT;
@@ -142,35 +142,17 @@ __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ 
 
 // ---- polynomial-kernel sums over tiles of row pairs, fp64 (the Gram sums of the kernel distance) -----------------------------
 // k(a_r, b_s) = (gamma <a_r, b_s> + coef0)^degree for 64 rows of a against 64 rows of b; a workgroup owns one tile pair for the
-// whole call and writes ONE double, the sum of its up to 4096 values.  moments_kernel's structure (256 threads, a 4 x 4 register
-// block each, plain v_fma_f64 for the reason stated there) with the operands the other way round: there the summed index is the
-// row and a staged slice is [row][64 columns]; here it is the feature, and a slice is 64 rows x PK features, kept as the rows lie
-// in memory ([row][feature]) so that a 16-byte LDS read brings 4 consecutive features of one row.
+// whole call and writes ONE double, the sum of its up to 4096 values.  The dots are rg_pairtile.h's tile (fp32 rows, PairDot):
+// its staging, its LDS layout and its arithmetic contract are stated there.
 //
-// LDS layout.  ds_read_b128 is served in groups of 16 lanes and banks by (byte address / 4) mod 64, i.e. a group is conflict-free
-// when its distinct addresses fall into distinct 16-byte slots of the 256-byte bank row.  The lanes of a group read the same
-// feature offset of different rows, so the slot is decided by row * PITCH.  PITCH must be a multiple of 4 floats (16-byte reads),
-// i.e. a whole number of slots.  With the rows of a thread adjacent (row = 4 t + p, as in moments_kernel) neighbouring lanes are
-// 4 * PITCH floats apart, a multiple of 4 slots: at most 4 distinct slots of the 16 whatever the padding, 4-way or worse.  So
-// a thread's rows are INTERLEAVED (row = t + 16 p) and PITCH = PK + 4 = 36 floats = 9 slots: lanes t = 0..15 land on slots
-// 9 t mod 16 -- all 16 distinct (9 is odd).  The b side of a 16-lane group holds all 16 values of tx; the a side holds two
-// values of ty (adjacent rows, 9 slots apart: distinct), the rest broadcast.
-// Staging writes (ds_write_b32, 32 lanes on 32 consecutive floats of a row) are conflict-free as well.
-//
-// Arithmetic (the contract of the header): every operand converted to fp64; dot summed sequentially in ascending feature order
-// by fma (the product of two fp32 values is exact in fp64, so fma == mul + add bit for bit); t = gamma * dot + coef0 as two
-// rounded operations (the build has contraction off; __dmul_rn / __dadd_rn say so in the code); v = t, t t, (t t) t.
-// Features past F and rows past na / nb are staged as zeros; adding an exact zero to a dot changes nothing, and the VALUES of
-// rows past the end are masked out of the sum (k(0, y) = coef0^degree is not zero).
+// On top of the dots: t = gamma * dot + coef0 as two rounded operations (the build has contraction off; __dmul_rn / __dadd_rn
+// say so in the code); v = t, t t, (t t) t.  A zero-padded row has dot 0 but k(0, y) = coef0^degree is not zero, so the VALUES
+// of rows past na / nb are masked out of the sum.
 //
 // Order of the tile's sum: fixed, and invariant under transposing the tile -- a thread adds v[p][p] in order and then the pairs
 // (v[p][q] + v[q][p]), p < q; thread (ty, tx) then pairs its partial with thread (tx, ty)'s; the 136 pair sums are added by a
 // fixed tree.  Addition commutes bit for bit, so the tile (tj, ti) of a two-operand call on (a, a) gives the bits of tile
 // (ti, tj): the symmetric form (each off-diagonal pair computed once, stored twice) returns exactly what the general form does.
-constexpr int PT = 64;            // rows per tile: 16 x 16 threads, 4 x 4 results each (rows t, t + 16, t + 32, t + 48)
-constexpr int PK = 32;            // features staged per pass
-constexpr int PITCH = PK + 4;     // floats per staged row (see above)
-
 __device__ __forceinline__ double polyk(double dot, double gamma, double coef0, int degree) {
   const double t = __dadd_rn(__dmul_rn(gamma, dot), coef0);
   if (degree == 1) return t;
@@ -182,67 +164,22 @@ __global__ __launch_bounds__(256) void polykernel_tile_sums_kernel(const float* 
                                                                    const float* __restrict__ b, int ldb, int nb, int F, double gamma,
                                                                    double coef0, int degree, double* __restrict__ sums,
                                                                    double* __restrict__ diag, int Ta, int Tb, int symmetric) {
-  __shared__ __attribute__((aligned(16))) float sa[PT][PITCH];
-  __shared__ __attribute__((aligned(16))) float sb[PT][PITCH];
+  __shared__ __attribute__((aligned(16))) float sa[PAIR_ROWS * PairStage<float>::PITCH];
+  __shared__ __attribute__((aligned(16))) float sb[PAIR_ROWS * PairStage<float>::PITCH];
   __shared__ double part[16][17];
   __shared__ double red[256];
   int ti, tj;
-  if (symmetric) {                                          // linear index -> (ti, tj) of the upper triangle, row by row
-    int rem = (int)blockIdx.x;
-    ti = 0;
-    while (rem >= Ta - ti) { rem -= Ta - ti; ++ti; }
-    tj = ti + rem;
+  if (symmetric) {
+    upper_triangle_tile((int)blockIdx.x, Ta, ti, tj);
   } else {
     ti = (int)(blockIdx.x / (unsigned)Tb);
     tj = (int)(blockIdx.x % (unsigned)Tb);
   }
   const bool same = symmetric && ti == tj;
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const long long i0 = (long long)ti * PT, j0 = (long long)tj * PT;
+  const long long i0 = (long long)ti * PAIR_ROWS, j0 = (long long)tj * PAIR_ROWS;
   double acc[4][4];
-#pragma unroll
-  for (int p = 0; p < 4; ++p)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-  const float (*bs)[PITCH] = same ? sa : sb;
-  for (int k0 = 0; k0 < F; k0 += PK) {
-    // stage PK features of the two row tiles: scalar loads, half a wave reads 32 consecutive floats of a row (any lda >= F, no
-    // alignment needed); nothing past row na / nb or feature F is read
-    for (int e = tid; e < PT * PK; e += 256) {
-      const int rr = e / PK, kk = e % PK;
-      const bool kin = k0 + kk < F;
-      const long long ra = i0 + rr, rb = j0 + rr;
-      sa[rr][kk] = (kin && ra < na) ? a[(size_t)ra * (size_t)lda + (size_t)(k0 + kk)] : 0.f;
-      if (!same) sb[rr][kk] = (kin && rb < nb) ? b[(size_t)rb * (size_t)ldb + (size_t)(k0 + kk)] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int k = 0; k < PK; k += 4) {
-      float4 av[4], bv[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) av[p] = *reinterpret_cast<const float4*>(&sa[ty + 16 * p][k]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) bv[q] = *reinterpret_cast<const float4*>(&bs[tx + 16 * q][k]);
-      // four features, in ascending order for every accumulator
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = fma((double)av[p].x, (double)bv[q].x, acc[p][q]);
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = fma((double)av[p].y, (double)bv[q].y, acc[p][q]);
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = fma((double)av[p].z, (double)bv[q].z, acc[p][q]);
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[p][q] = fma((double)av[p].w, (double)bv[q].w, acc[p][q]);
-    }
-    __syncthreads();
-  }
+  pair_tile_accumulate<float, PairDot>(a, lda, PairRowsFrom{i0, na}, b, ldb, PairRowsFrom{j0, nb}, F, same, sa, sb, acc);
   // the kernel values, rows past the end masked to an exact zero
   double v[4][4];
 #pragma unroll
@@ -310,7 +247,7 @@ extern "C" int rg_moments_update(const float* x, int ldx, int n, int F, double* 
   RG_REQUIRE(F >= 1 && n >= 0 && ldx >= F, RG_EINVAL, "moments_update: bad sizes n %d F %d ldx %d", n, F, ldx);
   if (n == 0) return RG_OK;
   RG_REQUIRE(x && s1 && s2, RG_EINVAL, "moments_update: null buffer");
-  const long long T = ((long long)F + MT - 1) / MT;
+  const long long T = pair_tiles(F);
   const long long tiles = T * (T + 1) / 2;
   RG_REQUIRE(tiles <= 0x7fffffffLL, RG_EUNSUPPORTED, "moments_update: F %d needs %lld tiles", F, tiles);
   hipLaunchKernelGGL(moments_kernel, dim3((unsigned)tiles), dim3(256), 0, rg_stream(stream), x, ldx, n, F, s1, s2, (int)T);
@@ -329,7 +266,7 @@ extern "C" int rg_polykernel_tile_sums(const float* a, int lda, int na, const fl
              "polykernel_tile_sums: diag is required in the symmetric form (b == NULL) and must be NULL with two operands");
   if (na == 0 || nb == 0) return RG_OK;
   RG_REQUIRE(a && sums, RG_EINVAL, "polykernel_tile_sums: null buffer");
-  const long long Ta = ((long long)na + PT - 1) / PT, Tb = ((long long)nb + PT - 1) / PT;
+  const long long Ta = pair_tiles(na), Tb = pair_tiles(nb);
   const long long tiles = symmetric ? Ta * (Ta + 1) / 2 : Ta * Tb;
   RG_REQUIRE(tiles <= 0x7fffffffLL, RG_EUNSUPPORTED, "polykernel_tile_sums: %d x %d rows need %lld tiles", na, nb, tiles);
   hipLaunchKernelGGL(polykernel_tile_sums_kernel, dim3((unsigned)tiles), dim3(256), 0, rg_stream(stream), a, lda, na,

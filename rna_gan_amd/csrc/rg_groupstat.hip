@@ -2,7 +2,7 @@
 // (rna_gan_amd.representation, rna_gan_amd.metrics.ConditioningFidelity): fp64 sums of feature rows PER GROUP (a patient's tiles)
 // and, between two sets of fp64 centroids, the rank of every row's designated partner among all rows of the other set.
 // Nothing here depends on the build's 16-bit storage type: both builds compile the same code.
-#include "rg_internal.h"
+#include "rg_pairtile.h"
 
 namespace {
 
@@ -53,70 +53,21 @@ __global__ __launch_bounds__(GS_COLS) void group_sums_kernel(const float* __rest
 }
 
 // ---- ranks of the designated partners, fp64 -----------------------------------------------------------------------------------
-// d2 as rg_knn.hip states it (one rounded subtraction per feature, fma(diff, diff, acc) in ascending f, from 0), on fp64 rows.
-// tile_dist2's structure: 256 threads, a 4 x 4 register block per thread with INTERLEAVED rows (row = t + 16 p); MK fp64 features
-// staged per pass as the rows lie in memory with a pitch of MK + 2 doubles = 144 bytes = 9 sixteen-byte slots -- the byte
-// geometry of the fp32 tiles there (32 floats + 4), so the bank analysis written in rg_fidstat.hip holds for these ds_read_b128
-// (two doubles of one row each).  Features past F and rows past the end are staged as zeros (fma(0, 0, acc) = acc bit for bit);
-// pairs of rows past the end are skipped by INDEX.
+// d2 is rg_pairtile.h's tile (PairDist2) on fp64 rows: one rounded subtraction per feature, fma(diff, diff, acc) in ascending f
+// from 0 -- its staging, its LDS layout and its contract are stated there; pairs of rows past the end are skipped by INDEX.
 //
 // A workgroup owns 64 query rows and every `split`-th tile of 64 rows of b.  It first computes the tile of its query rows against
 // THEIR OWN TARGET ROWS, gathered by index (the rows of b at target[r]): the diagonal of that tile is d*(r), with the bits that
 // the same pair has in any other tile -- the value does not depend on the tiling.  Then, per tile of b, every thread compares its
 // 16 values with d* and counts in registers; the counts of a row are integers, so they are added with integer atomics (LDS, then
 // one atomicAdd per row onto rank, which the entry point zeroes in the same call when split > 1): the same bits on every run.
-constexpr int MT = 64;            // rows per tile
-constexpr int MK = 16;            // fp64 features staged per pass
-constexpr int MPITCH = MK + 2;    // doubles per staged row
-
-// acc[p][q] = d2(a[i0 + ty + 16 p], b[brow[tx + 16 q]]); brow: 64 row indices of b in LDS, -1 = no row
-__device__ __forceinline__ void match_tile(const double* __restrict__ a, int lda, int na, long long i0, const double* __restrict__ b,
-                                           int ldb, const int* brow, int F, double (*sa)[MPITCH], double (*sb)[MPITCH],
-                                           double (&acc)[4][4]) {
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-#pragma unroll
-  for (int p = 0; p < 4; ++p)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
-  for (int k0 = 0; k0 < F; k0 += MK) {
-    // 16 lanes read 16 consecutive doubles of a row (any ld >= F); nothing past row na, a missing row of b or feature F is read
-    for (int e = tid; e < MT * MK; e += 256) {
-      const int rr = e / MK, kk = e % MK;
-      const bool kin = k0 + kk < F;
-      const long long ra = i0 + rr;
-      const int rb = brow[rr];
-      sa[rr][kk] = (kin && ra < na) ? a[(size_t)ra * (size_t)lda + (size_t)(k0 + kk)] : 0.0;
-      sb[rr][kk] = (kin && rb >= 0) ? b[(size_t)rb * (size_t)ldb + (size_t)(k0 + kk)] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int k = 0; k < MK; k += 2) {
-      double2 av[4], bv[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) av[p] = *reinterpret_cast<const double2*>(&sa[ty + 16 * p][k]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) bv[q] = *reinterpret_cast<const double2*>(&sb[tx + 16 * q][k]);
-      // two features, in ascending order for every accumulator
-#define RG_MATCH_STEP(c)                                                 \
-  _Pragma("unroll") for (int p = 0; p < 4; ++p) {                        \
-    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                      \
-      const double diff = __dsub_rn(av[p].c, bv[q].c);                   \
-      acc[p][q] = fma(diff, diff, acc[p][q]);                            \
-    }                                                                    \
-  }
-      RG_MATCH_STEP(x)
-      RG_MATCH_STEP(y)
-#undef RG_MATCH_STEP
-    }
-    __syncthreads();
-  }
-}
+constexpr int MT = PAIR_ROWS;     // rows per tile
 
 __global__ __launch_bounds__(256) void match_ranks_kernel(const double* __restrict__ a, int lda, int na, const double* __restrict__ b,
                                                           int ldb, int nb, int F, const int* __restrict__ target,
                                                           int* __restrict__ rank, double* __restrict__ dtarget, int Tb, int split) {
-  __shared__ __attribute__((aligned(16))) double sa[MT][MPITCH];
-  __shared__ __attribute__((aligned(16))) double sb[MT][MPITCH];
+  __shared__ __attribute__((aligned(16))) double sa[MT * PairStage<double>::PITCH];
+  __shared__ __attribute__((aligned(16))) double sb[MT * PairStage<double>::PITCH];
   __shared__ double dstar[MT];
   __shared__ int tgt[MT], brow[MT], rowcnt[MT];
   const int ti = (int)(blockIdx.x / (unsigned)split), part = (int)(blockIdx.x % (unsigned)split);
@@ -133,8 +84,11 @@ __global__ __launch_bounds__(256) void match_ranks_kernel(const double* __restri
     rowcnt[tid] = 0;
   }
   __syncthreads();
+  // acc[p][q] = d2(a[i0 + ty + 16 p], b[brow[tx + 16 q]]); brow: 64 row indices of b, -1 = no row
+  const PairRowsFrom arows{i0, na};
+  const PairRowsAt brows{brow};
   double acc[4][4];
-  match_tile(a, lda, na, i0, b, ldb, brow, F, sa, sb, acc);
+  pair_tile_accumulate<double, PairDist2>(a, lda, arows, b, ldb, brows, F, false, sa, sb, acc);
   if (ty == tx) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) dstar[ty + 16 * p] = acc[p][p];
@@ -152,7 +106,7 @@ __global__ __launch_bounds__(256) void match_ranks_kernel(const double* __restri
     __syncthreads();                                       // brow is free: everybody is past the previous tile's staging
     if (tid < MT) brow[tid] = j0 + tid < nb ? (int)(j0 + tid) : -1;
     __syncthreads();
-    match_tile(a, lda, na, i0, b, ldb, brow, F, sa, sb, acc);
+    pair_tile_accumulate<double, PairDist2>(a, lda, arows, b, ldb, brows, F, false, sa, sb, acc);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const long long s = j0 + tx + 16 * q;
@@ -204,7 +158,7 @@ extern "C" int rg_match_ranks(const double* a, int lda, int na, const double* b,
   RG_REQUIRE(target || na <= nb, RG_EINVAL, "match_ranks: no target and na %d > nb %d", na, nb);
   RG_REQUIRE(a && b && rank && dtarget, RG_EINVAL, "match_ranks: null buffer");
   if (na == 0) return RG_OK;
-  const long long Ta = ((long long)na + MT - 1) / MT, Tb = ((long long)nb + MT - 1) / MT;
+  const long long Ta = pair_tiles(na), Tb = pair_tiles(nb);
   // the tiles of b are dealt to `split` workgroups per 64 query rows while the query tiles alone leave compute units idle (each
   // part pays the d* tile again, so no more parts than that)
   long long split = 256 / Ta;

@@ -3,30 +3,25 @@
 // set in the balls of another.  Both are all-pairs SQUARED distances in fp64 over 64 x 64 tiles of row pairs with a selection or
 // a comparison per pair; the n x n matrix never exists in memory.
 // Nothing here depends on the build's 16-bit storage type: both builds compile the same code.
-#include "rg_internal.h"
+#include "rg_pairtile.h"
 
 #include <cmath>
 
 namespace {
 
 // ---- squared distances of a 64 x 64 tile of row pairs, fp64 -------------------------------------------------------------------
-// polykernel_tile_sums_kernel's structure (rg_fidstat.hip): one 256-thread workgroup per tile pair, a 4 x 4 register block per
-// thread with INTERLEAVED rows (row = t + 16 p), 32 features staged per pass as the rows lie in memory, PITCH = 36 floats -- the
-// bank analysis written there holds unchanged, the reads are the same.  The inner step is one v_add_f64 (the difference) and one
-// v_fma_f64 per element pair where the Gram sums issue one v_fma_f64.
-//
-// Arithmetic (the contract of the header): every operand converted to fp64; diff = a_f - b_f is ONE rounded subtraction;
-// d2 = fma(diff, diff, d2) sequentially in ascending f.  So d2 >= 0, d2(a, a) = 0, and d2(a, b) and d2(b, a) hold the same bits
-// (diff only changes sign); the value does not depend on the tiling.  Features past F and rows past the end are staged as zeros:
-// fma(0, 0, d2) = d2 bit for bit, and the pairs of rows past the end are skipped by INDEX further down.
-// The Gram form |a|^2 + |b|^2 - 2 <a, b> is not used: it cancels, can go negative and is not symmetric bit for bit.
+// rg_pairtile.h's tile for fp32 rows and PairDist2 -- the same staging, LDS layout and d2 contract (symmetric bit for bit,
+// independent of the tiling, the pairs of rows past the end skipped by INDEX), stated there -- written out here and NOT taken from
+// the template: through it the loops compile to the same instructions, but the code around them does not (the d2 stores pair up
+// into ds_write2_b64, 102 VGPRs for 108), and rg_radius_hits measured 0.3 to 0.5 % slower at 2048 x 2048 x 2048
+// (profiles/pair_tile_core.json).  tests/test_repr_ops_gpu.py holds this copy and the template's fp64 form to the same bits.
 //
 // The tile's 4096 values then go to LDS (pitch 65 doubles, over the staging buffers, which are dead by then) and one thread per
 // row walks its 64 values in column order.  Everything after d2 (k smallest, count, minimum) is independent of order: the same
 // bits on every run, no atomics.
-constexpr int DT = 64;            // rows per tile
-constexpr int DK = 32;            // features staged per pass
-constexpr int DPITCH = DK + 4;    // floats per staged row
+constexpr int DT = PAIR_ROWS;     // rows per tile
+constexpr int DK = PairStage<float>::K;          // features staged per pass
+constexpr int DPITCH = PairStage<float>::PITCH;  // floats per staged row
 constexpr int D2PITCH = DT + 1;   // doubles per row of the tile's d2 matrix in LDS
 constexpr int KMAX = 16;          // largest k of rg_knn_radii2
 constexpr size_t STAGE_BYTES = 2 * DT * DPITCH * sizeof(float);
@@ -112,9 +107,8 @@ __device__ __forceinline__ double nan_to_inf(double v) { return v != v ? (double
 __global__ __launch_bounds__(256) void knn_tile_kernel(const float* __restrict__ a, int lda, int n, int F, int k,
                                                        double* __restrict__ part, int T) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[TILE_LDS];
-  int rem = (int)blockIdx.x, ti = 0;                        // linear index -> (ti, tj) of the upper triangle, row by row
-  while (rem >= T - ti) { rem -= T - ti; ++ti; }
-  const int tj = ti + rem;
+  int ti, tj;
+  upper_triangle_tile((int)blockIdx.x, T, ti, tj);
   const bool same = ti == tj;
   const long long i0 = (long long)ti * DT, j0 = (long long)tj * DT;
   tile_dist2(a, lda, n, i0, a, lda, n, j0, F, same, smem);
@@ -208,14 +202,12 @@ __global__ __launch_bounds__(256) void hits_merge_kernel(const double* __restric
   if (count != nullptr) count[i] = total;
 }
 
-inline long long tiles_of(long long n) { return (n + DT - 1) / DT; }
-
 }  // namespace
 
 extern "C" size_t rg_pairdist_ws_bytes(int na, int nb, int k) {
   if (na < 0 || nb < 0 || k < 0 || k > KMAX) return 0;
   const size_t per_row = k > 0 ? (size_t)k * sizeof(double) : sizeof(double) + sizeof(int);
-  return (size_t)tiles_of(nb) * (size_t)na * per_row;
+  return (size_t)pair_tiles(nb) * (size_t)na * per_row;
 }
 
 extern "C" int rg_knn_radii2(const float* a, int lda, int n, int F, int k, void* ws, size_t ws_bytes, double* r2, void* stream) {
@@ -224,7 +216,7 @@ extern "C" int rg_knn_radii2(const float* a, int lda, int n, int F, int k, void*
   RG_REQUIRE(n >= k + 1, RG_EINVAL, "knn_radii2: k %d needs at least %d rows, got %d", k, k + 1, n);
   RG_REQUIRE(a && ws && r2, RG_EINVAL, "knn_radii2: null buffer");
   RG_REQUIRE(((uintptr_t)ws & 7u) == 0, RG_EINVAL, "knn_radii2: the workspace must be 8-byte aligned");
-  const long long T = tiles_of(n);
+  const long long T = pair_tiles(n);
   const long long tiles = T * (T + 1) / 2;
   RG_REQUIRE(tiles <= 0x7fffffffLL, RG_EUNSUPPORTED, "knn_radii2: %d rows need %lld tiles", n, tiles);
   const size_t need = rg_pairdist_ws_bytes(n, n, k);
@@ -246,7 +238,7 @@ extern "C" int rg_radius_hits(const float* a, int lda, int na, const float* b, i
   if (na == 0 || nb == 0) return RG_OK;
   RG_REQUIRE(a && b && ws && mind2, RG_EINVAL, "radius_hits: null buffer");
   RG_REQUIRE(((uintptr_t)ws & 7u) == 0, RG_EINVAL, "radius_hits: the workspace must be 8-byte aligned");
-  const long long Ta = tiles_of(na), Tb = tiles_of(nb);
+  const long long Ta = pair_tiles(na), Tb = pair_tiles(nb);
   const long long tiles = Ta * Tb;
   RG_REQUIRE(tiles <= 0x7fffffffLL, RG_EUNSUPPORTED, "radius_hits: %d x %d rows need %lld tiles", na, nb, tiles);
   const size_t need = rg_pairdist_ws_bytes(na, nb, 0);

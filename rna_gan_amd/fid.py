@@ -346,6 +346,14 @@ def _device_image_set(images, device=None):
     return x
 
 
+def device_feature_pair(images1, images2, feature_extractor, batch_size=2, device=None):
+    """the two (N, F) fp32 device feature sets of kid.calculate_kid and prdc.calculate_prdc: each image set (as
+    _device_image_set takes it) is uploaded once, then resized to 299 and extracted on the device"""
+    sets = (_device_image_set(images, device) for images in (images1, images2))
+    return tuple(device_features((x[i:i + batch_size] for i in range(0, x.shape[0], batch_size)), feature_extractor, resize=299,
+                                 value_range=(0, 1)) for x in sets)
+
+
 def fid_statistics_device(images, feature_extractor, batch_size=2, device=None):
     """(mu, sigma, n) of calculate_fid(on_device=True) for ONE image set: host (N, H, W, 3) uint8 / float in [0, 1] images
     (or a device tensor of that form) are uploaded once, then resized to 299, extracted and accumulated on the device."""

@@ -27,17 +27,32 @@ def _tiles(n):
     return (int(n) + TILE - 1) // TILE
 
 
-def _rows(x, what):
-    """(tensor, row stride) of an (n, F) fp32 device tensor as the kernel takes it: unit column stride, row stride >= F; any
-    other form is copied once (a row slice or a column slice of a wider tensor is NOT copied)"""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
-        raise TypeError("%s must be an (n, F) float32 tensor on the GPU" % what)
+def _stream(device):
+    """torch's current stream on ``device``, as the entry points of the library take it"""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _rows(x, what, dtype=torch.float32, no_columns=ValueError):
+    """(tensor, row stride) of an (n, F) device tensor of ``dtype`` (float32 or float64) as the row kernels take it: unit column
+    stride, row stride >= F; any other form is copied once (a row slice or a column slice of a wider tensor is NOT copied).
+    no_columns: the exception class for F = 0."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.dim() == 2):
+        raise TypeError("%s must be an (n, F) %s tensor on the GPU" % (what, str(dtype).replace("torch.", "")))
     if x.shape[1] < 1:
-        raise ValueError("%s has no feature columns" % what)
+        raise no_columns("%s has no feature columns" % what)
     F = x.shape[1]
     if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < F):
         x = x.contiguous()
     return x, (x.stride(0) if x.shape[0] > 1 else F)
+
+
+def _row_pair(a, b, names=("a", "b"), dtype=torch.float32, no_columns=ValueError):
+    """``_rows`` of two sets that must agree in F and lie on one device: (a, lda, b, ldb)"""
+    a, lda = _rows(a, names[0], dtype, no_columns)
+    b, ldb = _rows(b, names[1], dtype, no_columns)
+    if a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError("%s is %s on %s, %s is %s on %s" % (names[0], tuple(a.shape), a.device, names[1], tuple(b.shape), b.device))
+    return a, lda, b, ldb
 
 
 def _kernel_args(F, gamma, coef0, degree):
@@ -54,10 +69,9 @@ def _launch(a, lda, b, ldb, gamma, coef0, degree, sums, diag):
     """one rg_polykernel_tile_sums launch on the current stream; sums / diag: contiguous fp64 views that receive the result"""
     from . import _abi
     with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
         rc = _abi.load().rg_polykernel_tile_sums(a.data_ptr(), lda, a.shape[0], None if b is None else b.data_ptr(), ldb,
                                                  0 if b is None else b.shape[0], a.shape[1], gamma, coef0, degree,
-                                                 sums.data_ptr(), None if diag is None else diag.data_ptr(), stream)
+                                                 sums.data_ptr(), None if diag is None else diag.data_ptr(), _stream(a.device))
         _abi.check(rc, "rg_polykernel_tile_sums")
 
 
@@ -66,19 +80,17 @@ def polykernel_tile_sums(a, b=None, gamma=None, coef0=1.0, degree=3):
     sums is (ceil(na / 64), ceil(nb / 64)); b=None is the symmetric form (b = a, each tile pair computed once) and diag
     (ceil(na / 64),) then holds the per-tile sums of k(a_r, a_r); with b given diag is None.  gamma=None: 1 / F.
     Rows are read where they lie (a row or column slice of a wider tensor is not copied)."""
-    a, lda = _rows(a, "a")
-    gamma, coef0, degree = _kernel_args(a.shape[1], gamma, coef0, degree)
     if b is None:
-        sums = torch.zeros(_tiles(a.shape[0]), _tiles(a.shape[0]), dtype=torch.float64, device=a.device)
-        diag = torch.zeros(_tiles(a.shape[0]), dtype=torch.float64, device=a.device)
-        _launch(a, lda, None, lda, gamma, coef0, degree, sums, diag)
-        return sums, diag
-    b, ldb = _rows(b, "b")
-    if b.shape[1] != a.shape[1] or b.device != a.device:
-        raise ValueError("a is %s on %s, b is %s on %s" % (tuple(a.shape), a.device, tuple(b.shape), b.device))
-    sums = torch.zeros(_tiles(a.shape[0]), _tiles(b.shape[0]), dtype=torch.float64, device=a.device)
-    _launch(a, lda, b, ldb, gamma, coef0, degree, sums, None)
-    return sums, None
+        a, lda = _rows(a, "a")
+        ldb, Tb = lda, _tiles(a.shape[0])
+    else:
+        a, lda, b, ldb = _row_pair(a, b)
+        Tb = _tiles(b.shape[0])
+    kargs = _kernel_args(a.shape[1], gamma, coef0, degree)
+    sums = torch.zeros(_tiles(a.shape[0]), Tb, dtype=torch.float64, device=a.device)
+    diag = torch.zeros(Tb, dtype=torch.float64, device=a.device) if b is None else None
+    _launch(a, lda, b, ldb, *kargs, sums, diag)
+    return sums, diag
 
 
 def mmd2_from_sums(sxx, dx, syy, dy, sxy, m, n):
@@ -117,10 +129,7 @@ def _pair_value(host, at, m, n):
 
 
 def _check_pair(x, y):
-    x, ldx = _rows(x, "x")
-    y, ldy = _rows(y, "y")
-    if x.shape[1] != y.shape[1] or x.device != y.device:
-        raise ValueError("x is %s on %s, y is %s on %s" % (tuple(x.shape), x.device, tuple(y.shape), y.device))
+    x, ldx, y, ldy = _row_pair(x, y, ("x", "y"))
     if x.shape[0] < 2 or y.shape[0] < 2:
         raise ValueError("the unbiased MMD^2 needs at least 2 rows in each set, got %d and %d" % (x.shape[0], y.shape[0]))
     return x, ldx, y, ldy
@@ -180,10 +189,5 @@ def calculate_kid(images1, images2, feature_extractor, batch_size=2, device=None
     """Counterpart of fid.calculate_fid(on_device=True): images (N, H, W, 3) uint8 / float in [0, 1] are uploaded once, resized
     to 299 and extracted on the device (``feature_extractor`` returns device tensors, e.g. fid.inception_features_device);
     returns kernel_distance(features1, features2, **kwargs)."""
-    from . import fid as FID
-    feats = []
-    for images in (images1, images2):
-        x = FID._device_image_set(images, device)
-        feats.append(FID.device_features((x[i:i + batch_size] for i in range(0, x.shape[0], batch_size)), feature_extractor,
-                                         resize=299, value_range=(0, 1)))
-    return kernel_distance(feats[0], feats[1], **kwargs)
+    from .fid import device_feature_pair
+    return kernel_distance(*device_feature_pair(images1, images2, feature_extractor, batch_size, device), **kwargs)

@@ -23,7 +23,31 @@ rg_nn_topk_i8) and the fraction that is closer to one than any other training ti
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
+
+
+@contextlib.contextmanager
+def _eval_mode(*modules):
+    """the modules in eval mode; on the way out, however it is left, each is put back into the mode it was in"""
+    modes = [(m, m.training) for m in modules]
+    try:
+        for m, _ in modes:
+            m.eval()
+        yield
+    finally:
+        for m, was in modes:
+            m.train(was)
+
+
+def _feature_extractor(extractor, discriminator):
+    """``(extract, resize)`` of a metric's ``extractor`` setting: the discriminator trunk at native resolution (no resize), or
+    the callable behind a resize to 299 x 299"""
+    if extractor == "discriminator":
+        from .fid import discriminator_features_device
+        return discriminator_features_device(discriminator), None
+    return extractor, 299
 
 
 class EvaluationMetric:
@@ -46,68 +70,34 @@ class EvaluationMetric:
         raise NotImplementedError
 
 
-class _GeneratedAgainstReal(EvaluationMetric):
-    """What FrechetDistance, KernelDistance and PrecisionRecall share: the real set, the private noise, the batches of both image sets and the
-    evaluation frame (eval mode under no_grad, modes restored, the real set's result cached for a fixed extractor).  A subclass
-    supplies ``metric_ops`` and what is collected from a set's batches."""
+class _GeneratedSamples(EvaluationMetric):
+    """Draws ``n_fake`` generated images from private noise: what every metric that samples the generator shares.  The noise is
+    None ((n_fake, E) standard normal values drawn ONCE from a private torch.Generator(seed): at construction when
+    ``encoding_dims`` is given, else at the first evaluation from the generator's ``encoding_dims`` -- the same values either
+    way), a tensor of n_fake rows, or a callable noise(n) called at every evaluation.  ``count`` names n_fake in the messages
+    of the constructor; ``least`` is its smallest value."""
 
-    def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None):
+    def __init__(self, n_fake, noise, seed, batch_size, encoding_dims, count="n_fake", least=1):
         super().__init__()
-        if not (extractor == "discriminator" or callable(extractor)):
-            raise ValueError("extractor must be 'discriminator' or a callable device-side feature extractor")
-        self.extractor = extractor
+        self.n_fake = int(n_fake)
+        if self.n_fake < least:
+            raise ValueError("%s must be >= %d" % (count, least))
         self.seed = int(seed)
         self.batch_size = int(batch_size)
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         self._rng = torch.Generator().manual_seed(self.seed)
-        self._real_stats = None
-        self.real = None
-        self.set_real(real)
-        self.n_fake = int(n_fake) if n_fake is not None else int(self.real.shape[0])
-        if self.n_fake < 2:
-            raise ValueError("n_fake must be >= 2")
         if torch.is_tensor(noise) and noise.shape[0] != self.n_fake:
-            raise ValueError("noise has %d rows, n_fake is %d" % (noise.shape[0], self.n_fake))
+            raise ValueError("noise has %d rows, %s is %d" % (noise.shape[0], count, self.n_fake))
         self.noise = noise
         if noise is None and encoding_dims is not None:
             self.noise = torch.randn(self.n_fake, int(encoding_dims), generator=self._rng)
 
-    # ------------------------------------------------------------------ data
-    def set_real(self, real):
-        if not torch.is_tensor(real) or real.dim() != 4 or real.shape[1] != 3 or real.shape[0] < 2:
-            raise ValueError("real must be an (N >= 2, 3, S, S) tensor of tiles")
-        if real.dtype != torch.uint8 and not real.is_floating_point():
-            raise TypeError("real must be uint8 or float tiles")
-        self.real = real
-        self._real_stats = None
-
-    def __getstate__(self):
-        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
-                "extractor": self.extractor if isinstance(self.extractor, str) else "callable"}
-
     def __setstate__(self, state):
         self.__dict__.update(state)
-        self.real = None
         self.noise = None
-        self._real_stats = None
         self._rng = torch.Generator().manual_seed(self.seed)
 
-    # ------------------------------------------------------------------ torchgan's hooks
-    def preprocess(self, x):
-        """A chunk of the real set on the device, in the form its consumer takes: [-1, 1] fp32 for the discriminator (uint8
-        tiles through rg_u8_to_norm, the training input transform); unchanged for the resize kernel, which reads uint8."""
-        if self.extractor != "discriminator" or x.dtype != torch.uint8:
-            return x if x.dtype == torch.uint8 else x.float()
-        from . import _abi
-        x = x.contiguous()
-        y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _abi.check(_abi.load().rg_u8_to_norm(x.data_ptr(), y.data_ptr(), x.numel(), 0.5, 0.5,
-                                                 torch.cuda.current_stream(x.device).cuda_stream), "rg_u8_to_norm")
-        return y
-
-    # ------------------------------------------------------------------ evaluation
     def _noise_for(self, generator, device):
         if callable(self.noise):
             z = self.noise(self.n_fake)
@@ -128,6 +118,55 @@ class _GeneratedAgainstReal(EvaluationMetric):
             else:
                 yield generator(c.contiguous())
 
+    @torch.no_grad()
+    def generated_tiles(self, generator, device):
+        """The evaluation's uint8 tiles, one device tensor per batch (eval mode, the mode restored); for the metrics whose
+        ``preprocess`` turns generated images into tiles."""
+        with _eval_mode(generator):
+            z = self._noise_for(generator, device)
+            return [self.preprocess(img) for img in self._fake_batches(generator, z)]
+
+
+class _GeneratedAgainstReal(_GeneratedSamples):
+    """What FrechetDistance, KernelDistance and PrecisionRecall share: the real set, the batches of both image sets and the
+    evaluation frame (eval mode under no_grad, modes restored, the real set's result cached for a fixed extractor).  A subclass
+    supplies ``metric_ops`` and what is collected from a set's batches."""
+
+    def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None):
+        if not (extractor == "discriminator" or callable(extractor)):
+            raise ValueError("extractor must be 'discriminator' or a callable device-side feature extractor")
+        self.extractor = extractor
+        self._real_stats = None
+        self.real = None
+        self.set_real(real)
+        super().__init__(self.real.shape[0] if n_fake is None else n_fake, noise, seed, batch_size, encoding_dims, least=2)
+
+    # ------------------------------------------------------------------ data
+    def set_real(self, real):
+        if not torch.is_tensor(real) or real.dim() != 4 or real.shape[1] != 3 or real.shape[0] < 2:
+            raise ValueError("real must be an (N >= 2, 3, S, S) tensor of tiles")
+        if real.dtype != torch.uint8 and not real.is_floating_point():
+            raise TypeError("real must be uint8 or float tiles")
+        self.real = real
+        self._real_stats = None
+
+    def __getstate__(self):
+        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
+                "extractor": self.extractor if isinstance(self.extractor, str) else "callable"}
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.real = None
+        self._real_stats = None
+
+    # ------------------------------------------------------------------ torchgan's hooks
+    def preprocess(self, x):
+        """A chunk of the real set on the device, in the form its consumer takes: [-1, 1] fp32 for the discriminator (uint8
+        tiles through rg_u8_to_norm, the training input transform); unchanged for the resize kernel, which reads uint8."""
+        from .representation import _real_batch
+        return _real_batch(x, None if self.extractor == "discriminator" else 299, 0.5, 0.5)
+
+    # ------------------------------------------------------------------ evaluation
     def _real_batches(self, device):
         for i in range(0, self.real.shape[0], self.batch_size):
             yield self.preprocess(self.real[i:i + self.batch_size].to(device))
@@ -138,15 +177,8 @@ class _GeneratedAgainstReal(EvaluationMetric):
         ``_real_stats`` for a fixed extractor), both networks in eval mode, their modes restored"""
         if self.real is None:
             raise RuntimeError("%s: no real set (an unpickled metric keeps its settings only: call set_real)" % type(self).__name__)
-        from . import fid as FID
-        modes = [(m, m.training) for m in (generator, discriminator)]
-        try:
-            for m, _ in modes:
-                m.eval()
-            if self.extractor == "discriminator":
-                extract, resize = FID.discriminator_features_device(discriminator), None
-            else:
-                extract, resize = self.extractor, 299
+        with _eval_mode(generator, discriminator):
+            extract, resize = _feature_extractor(self.extractor, discriminator)
             z = self._noise_for(generator, device)
             fake = collect(self._fake_batches(generator, z), extract, resize)
             real = self._real_stats
@@ -155,9 +187,6 @@ class _GeneratedAgainstReal(EvaluationMetric):
                 if resize is not None:                       # a fixed extractor: the real set's result never changes
                     self._real_stats = real
             return fake, real
-        finally:
-            for m, was in modes:
-                m.train(was)
 
 
 class FrechetDistance(_GeneratedAgainstReal):
@@ -312,7 +341,7 @@ class PrecisionRecall(_GeneratedAgainstReal):
         return float(self.last[self.report])
 
 
-class TissueYield(EvaluationMetric):
+class TissueYield(_GeneratedSamples):
     """The fraction of generated tiles that the reference tiler's acceptance rule keeps (rna_gan_amd.tissue.accept: the dilated
     tissue mask covers more than ``min_tissue`` of the tile and the tile is not low-contrast) -- the rule every real training tile
     passed and no generated tile is otherwise held to.  No real set and no feature extractor: ``samples`` generated images go
@@ -329,30 +358,14 @@ class TissueYield(EvaluationMetric):
 
     def __init__(self, samples, min_tissue=0.2, rgb_min=50, dilate=3, percentiles=(1, 99), fraction=0.05, luma_range=2.0,
                  noise=None, seed=0, batch_size=256, encoding_dims=None):
-        super().__init__()
-        self.n_fake = int(samples)
-        if self.n_fake < 1:
-            raise ValueError("samples must be >= 1")
+        super().__init__(samples, noise, seed, batch_size, encoding_dims, count="samples")
         self.min_tissue, self.fraction, self.luma_range = float(min_tissue), float(fraction), float(luma_range)
         self.rgb_min, self.dilate, self.percentiles = int(rgb_min), int(dilate), tuple(float(q) for q in percentiles)
         from .tissue import MAX_DILATE, percentile_ranks
         if not 0 <= self.rgb_min <= 255 or not 0 <= self.dilate <= MAX_DILATE:
             raise ValueError("rgb_min must be in 0..255 and dilate in 0..%d" % MAX_DILATE)
         percentile_ranks(2, self.percentiles)                    # two percentiles in [0, 100]
-        self.seed = int(seed)
-        self.batch_size = int(batch_size)
-        if self.batch_size < 1:
-            raise ValueError("batch_size must be >= 1")
-        self._rng = torch.Generator().manual_seed(self.seed)
-        if torch.is_tensor(noise) and noise.shape[0] != self.n_fake:
-            raise ValueError("noise has %d rows, samples is %d" % (noise.shape[0], self.n_fake))
-        self.noise = noise
-        if noise is None and encoding_dims is not None:
-            self.noise = torch.randn(self.n_fake, int(encoding_dims), generator=self._rng)
         self.last, self.last_stats, self.history = None, None, []
-
-    _noise_for = _GeneratedAgainstReal._noise_for
-    _fake_batches = _GeneratedAgainstReal._fake_batches
 
     def __getstate__(self):
         return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
@@ -360,11 +373,9 @@ class TissueYield(EvaluationMetric):
                 "dilate": self.dilate, "percentiles": self.percentiles, "history": [dict(h) for h in self.history]}
 
     def __setstate__(self, state):
-        self.__dict__.update(state)
-        self.noise = None
+        super().__setstate__(state)
         self.last, self.last_stats = None, None
         self.history = [dict(h) for h in state.get("history", [])]
-        self._rng = torch.Generator().manual_seed(self.seed)
 
     def preprocess(self, x):
         """fp32 [-1, 1] NCHW images -> the uint8 tiles a store would hold (interleaved RGB, the rounding rule), on the device."""
@@ -377,17 +388,6 @@ class TissueYield(EvaluationMetric):
         return {"accepted": float(TQ.accept(stats, self.min_tissue, self.fraction, self.luma_range).sum()) / n,
                 "tissue_fraction": float(TQ.tissue_fraction(stats).sum()) / n,
                 "low_contrast": float(TQ.low_contrast(stats, self.fraction, self.luma_range).sum()) / n}
-
-    @torch.no_grad()
-    def generated_tiles(self, generator, device):
-        """The evaluation's uint8 tiles, one device tensor per batch (eval mode, the mode restored)."""
-        was = generator.training
-        try:
-            generator.eval()
-            z = self._noise_for(generator, device)
-            return [self.preprocess(img) for img in self._fake_batches(generator, z)]
-        finally:
-            generator.train(was)
 
     def metric_ops(self, generator, device):
         import numpy as np
@@ -492,16 +492,9 @@ class ConditioningFidelity(EvaluationMetric):
     def metric_ops(self, generator, discriminator, device):
         if self.real_tiles is None:
             raise RuntimeError("ConditioningFidelity: no data (an unpickled metric keeps its settings only: call set_data)")
-        from . import fid as FID
         from .representation import patient_representations
-        modes = [(m, m.training) for m in (generator, discriminator)]
-        try:
-            for m, _ in modes:
-                m.eval()
-            if self.extractor == "discriminator":
-                extract, resize = FID.discriminator_features_device(discriminator), None
-            else:
-                extract, resize = self.extractor, 299
+        with _eval_mode(generator, discriminator):
+            extract, resize = _feature_extractor(self.extractor, discriminator)
             real = self._real_centroids
             reps = patient_representations(extract, real=(self.real_tiles, self.patient_of) if real is None else None,
                                            conditioned=generator, betavae=self.betavae, gene_exp=self.rna,
@@ -514,12 +507,9 @@ class ConditioningFidelity(EvaluationMetric):
             self.last = self.calculate_score(reps["conditioned"], real)
             self.history.append(dict(self.last))
             return float(self.last[self.report])
-        finally:
-            for m, was in modes:
-                m.train(was)
 
 
-class Memorisation(EvaluationMetric):
+class Memorisation(_GeneratedSamples):
     """Is the generator reproducing its training tiles?  The one failure every metric above REWARDS: a memorised tile is perfect in
     fidelity, covers its real neighbour and follows its patient's expression row.  ``samples`` generated tiles go through
     ``synthesize`` -> ``export.tiles_u8(layout="nchw")`` and are searched against the int8 block-mean descriptors of the training
@@ -543,24 +533,11 @@ class Memorisation(EvaluationMetric):
 
     def __init__(self, train_tiles, samples, factor=4, k=1, d4=False, heldout=None, noise=None, seed=0, batch_size=256,
                  encoding_dims=None):
-        super().__init__()
+        super().__init__(samples, noise, seed, batch_size, encoding_dims, count="samples")
         from .nearest import FACTORS, K_MAX
-        self.n_fake = int(samples)
-        if self.n_fake < 1:
-            raise ValueError("samples must be >= 1")
         self.factor, self.k, self.d4 = int(factor), int(k), bool(d4)
         if self.factor not in FACTORS or not 1 <= self.k <= K_MAX:
             raise ValueError("factor must be one of %s and k in 1..%d" % (FACTORS, K_MAX))
-        self.seed = int(seed)
-        self.batch_size = int(batch_size)
-        if self.batch_size < 1:
-            raise ValueError("batch_size must be >= 1")
-        self._rng = torch.Generator().manual_seed(self.seed)
-        if torch.is_tensor(noise) and noise.shape[0] != self.n_fake:
-            raise ValueError("noise has %d rows, samples is %d" % (noise.shape[0], self.n_fake))
-        self.noise = noise
-        if noise is None and encoding_dims is not None:
-            self.noise = torch.randn(self.n_fake, int(encoding_dims), generator=self._rng)
         self.last, self.last_result, self.history = None, None, []
         self.train_tiles = self.heldout = self._index = None
         self.set_train(train_tiles, heldout)
@@ -568,9 +545,6 @@ class Memorisation(EvaluationMetric):
     @classmethod
     def from_tile_set(cls, ts, samples, **kwargs):
         return cls(ts.tiles, samples, **kwargs)
-
-    _noise_for = _GeneratedAgainstReal._noise_for
-    _fake_batches = _GeneratedAgainstReal._fake_batches
 
     def set_train(self, train_tiles, heldout=None):
         train_tiles = getattr(train_tiles, "tiles", train_tiles)
@@ -584,12 +558,10 @@ class Memorisation(EvaluationMetric):
                 "factor": self.factor, "k": self.k, "d4": self.d4, "history": [dict(h) for h in self.history]}
 
     def __setstate__(self, state):
-        self.__dict__.update(state)
-        self.noise = None
+        super().__setstate__(state)
         self.train_tiles = self.heldout = self._index = None
         self.last, self.last_result = None, None
         self.history = [dict(h) for h in state.get("history", [])]
-        self._rng = torch.Generator().manual_seed(self.seed)
 
     def preprocess(self, x):
         """fp32 [-1, 1] NCHW images -> planar uint8 tiles (the bytes a store would hold, the training set's layout), on the device."""
@@ -603,8 +575,6 @@ class Memorisation(EvaluationMetric):
         heldout = None if self.heldout is None else self.heldout.to(self._index.device)
         self.last_result = audit(generated_u8.to(self._index.device), self._index, k=self.k, d4=self.d4, heldout_u8=heldout)
         return self.last_result.summary()
-
-    generated_tiles = TissueYield.generated_tiles
 
     def metric_ops(self, generator, device):
         if self.train_tiles is None:

@@ -21,15 +21,11 @@ from __future__ import annotations
 
 import torch
 
-from .kid import _rows
+from . import _abi
+from .kid import _row_pair, _rows, _stream
 
 KMAX = 16
 _WS = {}            # device -> the cached workspace (one uint8 buffer per device, grown on demand)
-
-
-def _lib():
-    from . import _abi
-    return _abi, _abi.load()
 
 
 def _workspace(device, nbytes):
@@ -55,13 +51,12 @@ def knn_radii2(x, k):
     x, ldx = _rows(x, "x")
     n, F = x.shape
     k = _check_k(k, n, "x")
-    abi, lib = _lib()
-    need = lib.rg_pairdist_ws_bytes(n, n, k)
-    ws = _workspace(x.device, need)
+    lib = _abi.load()
+    ws = _workspace(x.device, lib.rg_pairdist_ws_bytes(n, n, k))
     r2 = torch.empty(n, dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
-        abi.check(lib.rg_knn_radii2(x.data_ptr(), ldx, n, F, k, ws.data_ptr(), ws.numel(), r2.data_ptr(),
-                                    torch.cuda.current_stream(x.device).cuda_stream), "rg_knn_radii2")
+        _abi.check(lib.rg_knn_radii2(x.data_ptr(), ldx, n, F, k, ws.data_ptr(), ws.numel(), r2.data_ptr(), _stream(x.device)),
+                   "rg_knn_radii2")
     return r2
 
 
@@ -69,10 +64,7 @@ def radius_hits(a, b, rb2=None):
     """``(count, mind2)`` for the rows of a (na, F) against the rows of b (nb, F), fp32 on one device: count[r] (int32) =
     #{ s : d2(a_r, b_s) <= rb2[s] } with rb2 the (nb,) fp64 squared radii of b's rows, mind2[r] (fp64) = min_s d2(a_r, b_s).
     rb2=None: count is None, only the minima are computed.  Rows are read where they lie."""
-    a, lda = _rows(a, "a")
-    b, ldb = _rows(b, "b")
-    if b.shape[1] != a.shape[1] or b.device != a.device:
-        raise ValueError("a is %s on %s, b is %s on %s" % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    a, lda, b, ldb = _row_pair(a, b)
     na, nb, F = a.shape[0], b.shape[0], a.shape[1]
     if na < 1 or nb < 1:
         raise ValueError("radius_hits needs at least one row in each set, got %d and %d" % (na, nb))
@@ -80,14 +72,14 @@ def radius_hits(a, b, rb2=None):
         if not (torch.is_tensor(rb2) and rb2.dtype == torch.float64 and rb2.device == a.device and rb2.shape == (nb,)):
             raise ValueError("rb2 must be an (nb,) float64 tensor on the device of a and b")
         rb2 = rb2.contiguous()
-    abi, lib = _lib()
+    lib = _abi.load()
     ws = _workspace(a.device, lib.rg_pairdist_ws_bytes(na, nb, 0))
     count = None if rb2 is None else torch.empty(na, dtype=torch.int32, device=a.device)
     mind2 = torch.empty(na, dtype=torch.float64, device=a.device)
     with torch.cuda.device(a.device):
-        abi.check(lib.rg_radius_hits(a.data_ptr(), lda, na, b.data_ptr(), ldb, nb, F, None if rb2 is None else rb2.data_ptr(),
-                                     ws.data_ptr(), ws.numel(), None if count is None else count.data_ptr(), mind2.data_ptr(),
-                                     torch.cuda.current_stream(a.device).cuda_stream), "rg_radius_hits")
+        _abi.check(lib.rg_radius_hits(a.data_ptr(), lda, na, b.data_ptr(), ldb, nb, F, None if rb2 is None else rb2.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), None if count is None else count.data_ptr(), mind2.data_ptr(),
+                                      _stream(a.device)), "rg_radius_hits")
     return count, mind2
 
 
@@ -97,10 +89,7 @@ def prdc(real_feats, fake_feats, k=5, real_radii2=None):
     ``knn_radii2(real_feats, k)``, is passed in), radii of the generated set, the generated rows in the real balls, the real rows
     in the generated balls (whose minima give coverage) -- then reductions over length-m / length-n vectors on the device and
     ONE download of the four values.  Comparisons are ``<=`` on squared distances (see the module docstring on ties)."""
-    x, _ = _rows(real_feats, "real_feats")
-    y, _ = _rows(fake_feats, "fake_feats")
-    if x.shape[1] != y.shape[1] or x.device != y.device:
-        raise ValueError("real_feats is %s on %s, fake_feats is %s on %s" % (tuple(x.shape), x.device, tuple(y.shape), y.device))
+    x, _, y, _ = _row_pair(real_feats, fake_feats, ("real_feats", "fake_feats"))
     m, n = x.shape[0], y.shape[0]
     k = _check_k(k, min(m, n), "the smaller set")
     if real_radii2 is None:
@@ -136,10 +125,5 @@ def calculate_prdc(images1, images2, feature_extractor, batch_size=2, device=Non
     """Counterpart of kid.calculate_kid: images (N, H, W, 3) uint8 / float in [0, 1] are uploaded once, resized to 299 and
     extracted on the device (``feature_extractor`` returns device tensors, e.g. fid.inception_features_device); images1 is the
     real set.  Returns prdc(features1, features2, **kwargs)."""
-    from . import fid as FID
-    feats = []
-    for images in (images1, images2):
-        x = FID._device_image_set(images, device)
-        feats.append(FID.device_features((x[i:i + batch_size] for i in range(0, x.shape[0], batch_size)), feature_extractor,
-                                         resize=299, value_range=(0, 1)))
-    return prdc(feats[0], feats[1], **kwargs)
+    from .fid import device_feature_pair
+    return prdc(*device_feature_pair(images1, images2, feature_extractor, batch_size, device), **kwargs)

@@ -21,14 +21,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-
-def _lib():
-    from . import _abi
-    return _abi, _abi.load()
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+from . import _abi
+from .kid import _row_pair, _rows, _stream
 
 
 class GroupMeans:
@@ -48,22 +42,18 @@ class GroupMeans:
     def update(self, feats, group):
         """feats (n, F) fp32 on the device (unit column stride, row stride >= F is read in place; any other form is copied once);
         group (n,) int32 ids on the device: rows with an id outside [0, G) are ignored."""
-        if not (torch.is_tensor(feats) and feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2):
-            raise TypeError("GroupMeans.update takes an (n, F) float32 tensor on the GPU")
+        feats, ldx = _rows(feats, "GroupMeans.update: feats")
         if feats.shape[1] != self.F or feats.device != self.sums.device:
             raise ValueError("GroupMeans.update: expected (n, %d) on %s, got %s on %s"
                              % (self.F, self.sums.device, tuple(feats.shape), feats.device))
         n = feats.shape[0]
         if not (torch.is_tensor(group) and group.dtype == torch.int32 and group.device == feats.device and tuple(group.shape) == (n,)):
             raise TypeError("GroupMeans.update takes the group ids as an (n,) int32 tensor on the features' device")
-        if feats.stride(1) != 1 or (n > 1 and feats.stride(0) < self.F):
-            feats = feats.contiguous()
         group = group.contiguous()
-        ldx = feats.stride(0) if n > 1 else self.F
-        abi, lib = _lib()
         with torch.cuda.device(self.sums.device):
-            abi.check(lib.rg_group_sums_update(feats.data_ptr(), ldx, n, self.F, group.data_ptr(), self.G, self.sums.data_ptr(),
-                                               self._counts.data_ptr(), _stream(self.sums.device)), "rg_group_sums_update")
+            _abi.check(_abi.load().rg_group_sums_update(feats.data_ptr(), ldx, n, self.F, group.data_ptr(), self.G, self.sums.data_ptr(),
+                                                        self._counts.data_ptr(), _stream(self.sums.device)),
+                       "rg_group_sums_update")
         self.n += n
         return self
 
@@ -102,23 +92,14 @@ def group_means(batches_with_ids, extractor, G, resize=None, value_range=None):
     return acc
 
 
-def _centroids(x, what):
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] >= 1):
-        raise TypeError("%s must be a (P, F) float64 tensor on the GPU" % what)
-    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
-        x = x.contiguous()
-    return x
-
-
 def match_ranks(query, ref, target=None, center=True):
     """``(rank int32, dtarget fp64)``, device tensors of len(query): for every row r of ``query`` (Pq, F) the rank of row
     target[r] of ``ref`` (Pr, F) among all rows of ref by squared distance to query[r] -- 0 = the designated partner is the
     nearest row, ties broken by index -- and that squared distance (rg_match_ranks).  Both sets are fp64 on one device.
     target: None (row r's partner is row r; needs Pq <= Pr) or Pq integers in [0, Pr).
     center=True: each set's own grand mean is subtracted first (see the module docstring)."""
-    query, ref = _centroids(query, "query"), _centroids(ref, "ref")
-    if query.shape[1] != ref.shape[1] or query.device != ref.device:
-        raise ValueError("query is %s on %s, ref is %s on %s" % (tuple(query.shape), query.device, tuple(ref.shape), ref.device))
+    # (P, 0) centroids have always been refused as a TypeError here
+    query, lda, ref, ldb = _row_pair(query, ref, ("query", "ref"), torch.float64, no_columns=TypeError)
     na, nb, F = query.shape[0], ref.shape[0], query.shape[1]
     if na < 1 or nb < 1:
         raise ValueError("match_ranks needs at least one row in each set, got %d and %d" % (na, nb))
@@ -133,15 +114,14 @@ def match_ranks(query, ref, target=None, center=True):
             raise ValueError("target points outside ref")
         target = target.to(device=query.device, dtype=torch.int32).contiguous()
     if center:
-        query = query - query.mean(dim=0, keepdim=True)
-        ref = ref - ref.mean(dim=0, keepdim=True)
+        query, ref = (query - query.mean(dim=0, keepdim=True)).contiguous(), (ref - ref.mean(dim=0, keepdim=True)).contiguous()
+        lda = ldb = F
     rank = torch.empty(na, dtype=torch.int32, device=query.device)
     dtarget = torch.empty(na, dtype=torch.float64, device=query.device)
-    abi, lib = _lib()
     with torch.cuda.device(query.device):
-        abi.check(lib.rg_match_ranks(query.data_ptr(), query.stride(0) if na > 1 else F, na, ref.data_ptr(),
-                                     ref.stride(0) if nb > 1 else F, nb, F, None if target is None else target.data_ptr(),
-                                     rank.data_ptr(), dtarget.data_ptr(), _stream(query.device)), "rg_match_ranks")
+        _abi.check(_abi.load().rg_match_ranks(query.data_ptr(), lda, na, ref.data_ptr(), ldb, nb, F,
+                                              None if target is None else target.data_ptr(), rank.data_ptr(), dtarget.data_ptr(),
+                                              _stream(query.device)), "rg_match_ranks")
     return rank, dtarget
 
 
@@ -182,11 +162,10 @@ def conditioned_noise(generator, betavae, gene_exp, tiles_per_patient, seed, gro
         latent_prep = generator.runtime()[0].latent_prep
     else:
         def latent_prep(u, z):
-            abi, lib = _lib()
             out = torch.empty_like(u)
             with torch.cuda.device(device):
-                abi.check(lib.rg_latent_prep(u.data_ptr(), z.data_ptr(), out.data_ptr(), u.shape[0], u.shape[1], _stream(device)),
-                          "rg_latent_prep")
+                _abi.check(_abi.load().rg_latent_prep(u.data_ptr(), z.data_ptr(), out.data_ptr(), u.shape[0], u.shape[1],
+                                                      _stream(device)), "rg_latent_prep")
             return out
     betavae = betavae.to(device)
     was_training = betavae.training
@@ -210,11 +189,11 @@ def _real_batch(x, resize, mean, std):
     resolution, uint8 tiles normalised by the training input transform (rg_u8_to_norm)"""
     if resize is not None or x.dtype != torch.uint8:
         return x if x.dtype == torch.uint8 else x.float()
-    abi, lib = _lib()
     x = x.contiguous()
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        abi.check(lib.rg_u8_to_norm(x.data_ptr(), y.data_ptr(), x.numel(), float(mean), float(std), _stream(x.device)), "rg_u8_to_norm")
+        _abi.check(_abi.load().rg_u8_to_norm(x.data_ptr(), y.data_ptr(), x.numel(), float(mean), float(std), _stream(x.device)),
+                   "rg_u8_to_norm")
     return y
 
 

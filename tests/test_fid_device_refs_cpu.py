@@ -257,6 +257,28 @@ def test_frechet_distance_pickles_settings_only():
     assert pickle.loads(pickle.dumps(FrechetDistance(real, extractor=lambda x: x))).extractor == "callable"
 
 
+def test_pickled_state_of_every_metric_keeps_its_keys():
+    """the keys a checkpoint holds per metric, as literals: a checkpoint written by an earlier version must go on loading"""
+    from rna_gan_amd.metrics import ConditioningFidelity, KernelDistance, Memorisation, PrecisionRecall, TissueYield
+    real = torch.zeros(8, 3, 32, 32, dtype=torch.uint8)
+    cases = [
+        (FrechetDistance(real), {"arg_map", "n_fake", "seed", "batch_size", "extractor"}),
+        (KernelDistance(real), {"arg_map", "n_fake", "seed", "batch_size", "extractor", "num_subsets", "subset_size", "degree",
+                                "gamma", "coef0"}),
+        (PrecisionRecall(real), {"arg_map", "n_fake", "seed", "batch_size", "extractor", "nearest_k", "report", "history"}),
+        (TissueYield(8), {"arg_map", "n_fake", "seed", "batch_size", "min_tissue", "fraction", "luma_range", "rgb_min", "dilate",
+                          "percentiles", "history"}),
+        (ConditioningFidelity(real, torch.arange(8) % 2, torch.zeros(2, 5), None),
+         {"arg_map", "tiles_per_patient", "seed", "batch_size", "group", "center", "report", "extractor", "history"}),
+        (Memorisation(real, 8), {"arg_map", "n_fake", "seed", "batch_size", "factor", "k", "d4", "history"}),
+    ]
+    for metric, keys in cases:
+        state = metric.__getstate__()
+        assert set(state) == keys, type(metric).__name__
+        back = pickle.loads(pickle.dumps(metric))
+        assert type(back) is type(metric) and back.__getstate__() == state, type(metric).__name__
+
+
 def test_frechet_distance_noise_is_private_and_repeatable():
     real = torch.zeros(8, 3, 32, 32, dtype=torch.uint8)
     torch.manual_seed(11)

@@ -17,7 +17,11 @@ included (repr_refs.integer_rows plants duplicates of the target row on both sid
 tile and over three tiles; nb <= 64 takes the path that writes rank directly, nb > 64 the one that shares the tiles of b out and
 adds with integer atomics; 65 x 8262 makes two of the 128 parts walk a second tile.  General floats: device and restatement are
 each within GAMMA(F) of the exact d2 (prdc_refs.GAMMA), so |d*_dev - d*_ref| <= 2 GAMMA max and the device rank lies between the
-restatement's ranks at d* (1 - 2 GAMMA) and d* (1 + 2 GAMMA)."""
+restatement's ranks at d* (1 - 2 GAMMA) and d* (1 + 2 GAMMA).
+
+The float and the double distance paths: rg_radius_hits on fp32 rows and rg_match_ranks on the same rows widened to fp64 are the
+same sequence of fp64 operations on the same values (rna_gan_amd/csrc/rg_pairtile.h; zero padding is fma(0, 0, acc) = acc), so
+their d2 must hold the same bits on general floats -- no tolerance."""
 import numpy as np
 import pytest
 import torch
@@ -355,6 +359,32 @@ def test_match_ranks_general_floats_and_graph_replay(half):
     assert _same_bits(sums.t.cpu().numpy(), wsums) and np.array_equal(counts.t.cpu().numpy(), wcounts)
     assert np.array_equal(grank.t.cpu().numpy(), rank) and _same_bits(gd.t.cpu().numpy(), d)
     assert sums.intact() and counts.intact() and grank.intact() and gd.intact()
+
+
+@pytest.mark.parametrize("half", BUILDS)
+@pytest.mark.parametrize("F", [33, 70])
+def test_float_and_double_distance_paths_hold_the_same_bits(half, F):
+    """d2(a_r, b_t) as rg_radius_hits states it (fp32 rows, 32 features per pass: its mind2 against the ONE row b_t) equals, under
+    == on the int64 views, d2 as rg_match_ranks states it (the rows widened to fp64, 16 features per pass: its dtarget with
+    target = t everywhere).  70 and 67 rows straddle the 64-row tile, F = 33 and 70 one fp32 pass and the fp64 passes."""
+    lib = _abi.load(half)
+    a, b = wide_floats(70, F, seed=300 + F), wide_floats(67, F, seed=400 + F)
+    da, db = Rows(a, F + 5, 1), Rows(b, F + 3)
+    wa, wb = RowsD(a, F + 2), RowsD(b, F + 1, 1)               # np.float64(fp32 value): exact
+    need = lib.rg_pairdist_ws_bytes(70, 1, 0)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    for t in (0, 63, 64, 66):
+        mind2, rank, dt, tg = GuardedD((70,)), GuardedI(70), GuardedD((70,)), Ints(np.full(70, t), BAD_TARGET)
+        rc = lib.rg_radius_hits(da.ptr, da.ld, 70, db.ptr + 4 * t * db.ld, db.ld, 1, F, None, ws.data_ptr(), need, None,
+                                mind2.t.data_ptr(), None)
+        assert rc == 0, lib.rg_last_error()
+        rc = lib.rg_match_ranks(wa.ptr, wa.ld, 70, wb.ptr, wb.ld, 67, F, tg.ptr, rank.t.data_ptr(), dt.t.data_ptr(), None)
+        assert rc == 0, lib.rg_last_error()
+        torch.cuda.synchronize()
+        assert mind2.intact() and rank.intact() and dt.intact()
+        f32, f64 = mind2.t.cpu().numpy(), dt.t.cpu().numpy()
+        assert np.isfinite(f32).all() and (f32 > 0).all(), "%s F=%d t=%d: a row or column past the operand was read" % (half, F, t)
+        assert np.array_equal(f32.view(np.int64), f64.view(np.int64)), "%s F=%d t=%d: the fp32 and the fp64 path differ" % (half, F, t)
 
 
 @pytest.mark.parametrize("half", BUILDS)
