@@ -488,6 +488,54 @@ int rg_group_sums_update(const float* x, int ldx, int n, int F, const int32_t* g
 int rg_match_ranks(const double* a, int lda, int na, const double* b, int ldb, int nb, int F, const int32_t* target, int32_t* rank,
                    double* dtarget, void* stream);
 
+/* The three primitives of the linear-probe scores (rg_linprobe.hip; rna_gan_amd.linprobe: the classifier two-sample test and
+ * train-on-synthetic, tissue_probe.py): multinomial logistic regression on fp32 feature rows that stay on the device.  One objective
+ * evaluation is scores, residual, column sums.  Everything is fp64, in a fixed order, without atomics: the same bits on every
+ * run.  No 16-bit type is involved: both builds behave identically.  Every call: no allocation, no host synchronisation, safe
+ * under graph capture, offsets computed in 64 bits; on an error nothing is launched.
+ * rg_linear_scores_f64: x is n rows of F fp32 features, row stride ldx >= F elements, any alignment; w is [C][F] fp64, row stride
+ *   ldw >= F; bias is [C] fp64 or NULL; z is [n][C] fp64, row stride ldz >= C, WRITTEN (not accumulated into):
+ *     acc = 0.0;  acc = fma((double)x[r][f], w[c][f], acc) for f = 0 .. F - 1 in ascending order;
+ *     z[r][c] = acc + bias[c]  (ONE rounded addition), or acc when bias == NULL.
+ *   One chain per (r, c), never split over F: the value does not depend on tiling or launch plan and equals a sequential loop
+ *   bit for bit (the product of an fp32 and an fp64 value is not exact, so the fma is part of the contract).  Any C >= 1.
+ *   Only rows < n and columns < F of x, rows < C and columns < F of w are read; nothing outside z[r][0 .. C) is written (the
+ *   columns C .. ldz of a row of z keep their contents).  n == 0: RG_OK, nothing launched.  RG_EINVAL for a NULL x, w or z,
+ *   F < 1, C < 1, n < 0, ldx < F, ldw < F or ldz < C; RG_EUNSUPPORTED for more than 2^31 - 1 workgroups (ceil(n / 32) ceil(C / 8)).
+ * rg_softmax_residual_f64: z is [n][C] fp64 logits, row stride ldz >= C; label is n int32; weight is n fp64 or NULL (= 1.0);
+ *   resid is [n][C] fp64, row stride ldr >= C, and row_loss is n fp64, both WRITTEN.  Per row r, with y = label[r], wt = weight[r]:
+ *     m = max_c z_c;  e_c = exp(z_c - m);  s = sum_c e_c in ascending c from 0.0;  p_c = e_c / s
+ *     0 <= y < C:  resid[r][c] = wt * (p_c - [c == y]),  row_loss[r] = wt * (log(s) - (z_y - m))
+ *     otherwise the row is MASKED: resid[r][0 .. C) are exact zeros and row_loss[r] is exact 0, whatever its logits and weight
+ *     hold (this is how rows are held out of a fit without gathering the others: the caller labels them -1).
+ *   m >= every z_c, so no exp overflows and s >= 1: logits of +-1e3 give finite results.  A NaN logit makes m NaN and with it
+ *   the whole of ITS row (resid and row_loss), and no other row.  exp and log are the device's fp64 functions: the results are
+ *   accurate to a few units in the last place, not bit-defined.  n == 0: RG_OK, nothing launched.  RG_EINVAL for a NULL z,
+ *   label, resid or row_loss, C < 1, n < 0, ldz < C or ldr < C.
+ * rg_rows_weighted_colsums_f64: x as above; r is [n][C] fp64, row stride ldr >= C; out is [C][F] fp64 row-major, WRITTEN:
+ *     out[c][f] = sum over the rows of r[row][c] * t(x[row][f]),   t(v) = (double)v for power == 1,
+ *                                                                  t(v) = (double)v * (double)v for power == 2 (exact in fp64).
+ *   The order of the sum is part of the contract.  The rows are cut into blocks of RG_COLSUM_ROWS; inside a block an entry is
+ *   ONE chain acc = fma(r[row][c], t, acc) in ascending row order from 0.0; the block partials of an entry are then added in
+ *   ascending block order from 0.0.  So the result is the same whatever the grid, and equals that loop bit for bit.
+ *   Two launches: the partials into ws ([blocks][C][F] fp64, rg_colsums_ws_bytes(n, F, C) bytes, 8-byte aligned, contents
+ *   irrelevant before and after), then a finisher.  With r a column of ones (C = 1) it gives column sums (power 1) and sums of
+ *   squares (power 2); with r = resid it gives the gradient of the loss with respect to W.
+ *   Only rows < n and columns < F of x, columns < C of r are read; nothing outside out[C][F] and the first
+ *   rg_colsums_ws_bytes(n, F, C) bytes of ws is written.  n == 0: RG_OK, out is written as the empty sums (+0.0 in every entry,
+ *   the finisher alone is launched); x, r and ws are then not looked at and may be NULL.  RG_EINVAL for a NULL out, a NULL x, r
+ *   or ws with n > 0, F < 1, C < 1, n < 0, ldx < F, ldr < C or a power other than 1 and 2; RG_EWORKSPACE (n > 0) for a ws that is
+ *   not 8-byte aligned or ws_bytes below the size above; RG_EUNSUPPORTED for more than 2^31 - 1 workgroups
+ *   (ceil(n / 256) ceil(F / 64) ceil(C / 8)).  rg_colsums_ws_bytes is 0 for arguments out of range. */
+#define RG_COLSUM_ROWS 256
+int rg_linear_scores_f64(const float* x, int ldx, int n, int F, const double* w, int ldw, int C, const double* bias, double* z,
+                         int ldz, void* stream);
+int rg_softmax_residual_f64(const double* z, int ldz, int n, int C, const int32_t* label, const double* weight, double* resid,
+                            int ldr, double* row_loss, void* stream);
+size_t rg_colsums_ws_bytes(int n, int F, int C);
+int rg_rows_weighted_colsums_f64(const float* x, int ldx, int n, int F, const double* r, int ldr, int C, int power, void* ws,
+                                 size_t ws_bytes, double* out, void* stream);
+
 /* ---- split-K conv + train-mode BatchNorm without the intermediate passes (bf16 path) -------------------------------
  * The deep Conv2d / ConvTranspose2d layers at small batch run split-K (rg_conv_split(...) > 1): every launch leaves
  * nsplit fp32 slabs [nsplit][rows][C] in the workspace.  rg_conv_down_partial / rg_conv_up_partial run ONLY that launch

@@ -179,6 +179,10 @@ PROTOTYPES = {
     "rg_radius_hits": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _z, _p, _p, _p]),
     "rg_group_sums_update": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
     "rg_match_ranks": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "rg_linear_scores_f64": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _i, _p]),
+    "rg_softmax_residual_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
+    "rg_colsums_ws_bytes": (_z, [_i, _i, _i]),
+    "rg_rows_weighted_colsums_f64": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _z, _p, _p]),
     "rg_conv_split": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rg_conv_slab_dtype": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rg_conv_down_partial": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
@@ -218,7 +222,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES when an existing entry
-# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three, rg_tile_gather_transform, rg_rows_gather_f32, rg_groupstat.hip's two, rg_stain.hip's four, rg_nn.hip's three) keeps the number -- load() refuses a library that lacks it
+# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three, rg_tile_gather_transform, rg_rows_gather_f32, rg_groupstat.hip's two, rg_stain.hip's four, rg_nn.hip's three, rg_linprobe.hip's four) keeps the number -- load() refuses a library that lacks it
 ABI_VERSION = 618
 
 _libs = {}

@@ -284,3 +284,63 @@ def patient_representations(extractor, real=None, conditioned=None, unconditione
                 pos += img.shape[0]
         out["unconditioned"] = group_means(batches(), extractor, P, resize=resize, value_range=(-1, 1)).means()
     return out
+
+
+def _feature_rows(batches_with_ids, extractor, resize=None, value_range=None):
+    """group_means' loop and checks without the reduction: ``(feats (n, F) fp32, ids (n,) int32)``, device tensors, of an iterable
+    of (device image batch, (n,) int32 device ids)"""
+    from .fid import preprocess_images_device
+    feats, rows = [], []
+    for batch, ids in batches_with_ids:
+        if resize is not None:
+            batch = preprocess_images_device(batch, resize, value_range)
+        f = extractor(batch)
+        if not (torch.is_tensor(f) and f.is_cuda):
+            raise TypeError("tile_features needs an extractor that returns device tensors (discriminator_features_device, "
+                            "inception_features_device)")
+        if f.dim() != 2 or f.shape[0] != ids.shape[0] or (feats and (f.shape[1] != feats[0].shape[1] or f.device != feats[0].device)):
+            raise ValueError("tile_features: the extractor returned %s for %d ids%s" % (
+                tuple(f.shape), ids.shape[0], " after (n, %d)" % feats[0].shape[1] if feats else ""))
+        feats.append(f.float())
+        rows.append(ids)
+    if not feats:
+        raise ValueError("tile_features: no batches")
+    return torch.cat(feats).contiguous(), torch.cat(rows).contiguous()
+
+
+@torch.no_grad()
+def tile_features(extractor, real=None, conditioned=None, *, betavae=None, gene_exp=None, tiles_per_patient=None, seed=0,
+                  batch_size=256, group=4096, resize=None, mean=0.5, std=0.5):
+    """``patient_representations`` without the reduction: per source a pair ``(feats (n, F) fp32, row (n,) int32)`` of device
+    tensors -- the features of every tile with the index of the patient (expression row) it belongs to -- for what needs the
+    tiles themselves rather than centroids (rna_gan_amd.linprobe.tstr, tissue_probe.py).
+
+    "real"         ``real = (tiles, patient_of)``: as ``real_representations`` takes it; the rows come back in tile order.
+    "conditioned"  ``conditioned``: a generator; ``tiles_per_patient`` tiles per row of ``gene_exp`` from
+                   ``conditioned_noise(..., seed, group)`` -- the SAME noise, so the same generated tiles, as the "conditioned"
+                   source of ``patient_representations`` for the same seed -- in its tile-major order."""
+    out = {}
+    if real is not None:
+        tiles, patient_of = real
+        patient_of = torch.as_tensor(patient_of)
+        if tiles.dim() != 4 or patient_of.shape[0] != tiles.shape[0] or tiles.shape[0] < 1:
+            raise ValueError("real: one patient id per tile, at least one tile")
+        device = tiles.device if tiles.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        patient_of = patient_of.to(device=device, dtype=torch.int32)
+
+        def batches():
+            for i in range(0, tiles.shape[0], batch_size):
+                yield _real_batch(tiles[i:i + batch_size].to(device), resize, mean, std), patient_of[i:i + batch_size]
+        out["real"] = _feature_rows(batches(), extractor, resize, None if tiles.dtype == torch.uint8 else (-1, 1))
+    if conditioned is not None:
+        if betavae is None or gene_exp is None or tiles_per_patient is None:
+            raise ValueError("a conditioned generator needs betavae, gene_exp and tiles_per_patient")
+
+        def batches():
+            for patient, z in conditioned_noise(conditioned, betavae, gene_exp, int(tiles_per_patient), seed, group):
+                pos = 0
+                for img in _generated(conditioned, z.float(), batch_size):
+                    yield img, patient[pos:pos + img.shape[0]]
+                    pos += img.shape[0]
+        out["conditioned"] = _feature_rows(batches(), extractor, resize, (-1, 1))
+    return out
