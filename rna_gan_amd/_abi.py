@@ -280,3 +280,18 @@ def check(rc: int, what: str):
                 if m:
                     msgs.append(m.decode() if len(_libs) == 1 else "[%s build] %s" % (h, m.decode()))
         raise RuntimeError("rna_gan_amd: %s failed (%d): %s" % (what, rc, " | ".join(msgs) if msgs else "?"))
+
+
+def launch(name: str, device, *args):
+    """One call of the bf16 library's entry point ``name``, whose LAST parameter is the stream: ``args`` are all the others, the
+    call is made with ``device`` current and on torch's current stream of it, and its return code is checked under ``name``.  A
+    small host operand goes in as a ctypes array where the prototype says c_void_p."""
+    import torch
+    with torch.cuda.device(device):
+        check(getattr(load(), name)(*args, torch.cuda.current_stream(device).cuda_stream), name)
+
+
+def device_key(device):
+    """(type, index) of a torch device, the current device's index where it has none: the key of a per-device cache"""
+    import torch
+    return device.type, device.index if device.index is not None else torch.cuda.current_device()

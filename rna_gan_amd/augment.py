@@ -95,11 +95,8 @@ class InputTransform:
             # pinned staging from torch's caching host allocator: a block is handed out again only once the non-blocking copy
             # that read it has completed, so the host never waits and no buffer is overwritten under a copy in flight
             dcodes = torch.from_numpy(codes).pin_memory().to(device, non_blocking=True)
-        with torch.cuda.device(device):
-            _abi.check(_abi.load().rg_tile_transform(
-                src.data_ptr(), _abi.RG_U8 if src.dtype == torch.uint8 else _abi.RG_F32, out.data_ptr(), N, C, S,
-                0 if dcodes is None else dcodes.data_ptr(), self.mean, self.std,
-                torch.cuda.current_stream(device).cuda_stream), "rg_tile_transform")
+        _abi.launch("rg_tile_transform", device, src.data_ptr(), _abi.RG_U8 if src.dtype == torch.uint8 else _abi.RG_F32,
+                    out.data_ptr(), N, C, S, 0 if dcodes is None else dcodes.data_ptr(), self.mean, self.std)
         return out
 
     def __call__(self, images, device):

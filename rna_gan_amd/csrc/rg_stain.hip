@@ -9,12 +9,11 @@
 //   rg_stain_conc_hist   the two stain concentrations of EVERY pixel: 2 x bins uint64
 //   rg_stain_apply       src -> dst bytes, one pass, in place when dst == src
 //
-// Launch plan of the three statistics kernels: a workgroup of 256 lanes owns SN_CHUNK consecutive pixels.  An interleaved set is one
-// stream of N H W pixels (the fit is over the set, tiles do not matter); a planar set is chunked per tile.  Tables are staged in LDS;
-// counting is 32-bit integer LDS atomics (a chunk is far below 2^32 pixels), then ONE 64-bit global integer atomic per occupied bin
-// per workgroup -- tq_hist_kernel's scheme (rg_tissue.hip).  Integer adds commute: no result depends on the launch plan, on the
-// batching or on the order of accumulating calls.  A lane takes 4 pixels from three dword loads where the base is 4-byte aligned
-// (and, planar, H W % 4 == 0), single bytes otherwise; both give the same integers.
+// Launch plan: every kernel reads its pixels through the stream of rg_u8px.h (layouts, the dword path, the in-place rule are stated
+// there), SN_CHUNK pixels per workgroup in the statistics kernels and SN_APPLY_CHUNK in apply; an interleaved set is one stream
+// (the fit is over the set, tiles do not matter).  Tables are staged in LDS; counting is 32-bit integer LDS atomics (a chunk is far
+// below 2^32 pixels), then ONE 64-bit global integer atomic per occupied bin per workgroup.  Integer adds commute: no result
+// depends on the launch plan, on the batching or on the order of accumulating calls.
 //
 // Narrowed arithmetic (the contract's sums are exact in int64; these keep the same bits):
 //   moments   |od| <= 23170, so a product fits int32 and the sum of FOUR products stays below 2^31: a lane sums a quad in int32 and
@@ -24,7 +23,7 @@
 //   conc, apply  the host checks the ranges of its operands: when every factor fits int32 the kernels are instantiated on int
 //             (32 x 32 -> 64 multiply-adds), else on long long.
 // No 16-bit type is involved: both builds behave identically.
-#include "rg_common.h"
+#include "rg_u8px.h"
 
 namespace {
 
@@ -34,65 +33,6 @@ constexpr int SN_KMAX = 2048;          // angle bins
 constexpr int SN_BINSMAX = 4096;       // concentration bins per stain
 constexpr int SN_LMAX = 8192;          // entries of the output table
 constexpr long long SN_MAXPIX = 1LL << 33;
-
-struct sn_geom {
-  long long HW;      // pixels per tile (planar), or of the whole set (interleaved)
-  unsigned chunks;   // workgroups per tile
-  int chunk, planar, reverse, vec;
-};
-
-__device__ __forceinline__ int sn_byte(const uint32_t* w, int k) { return (int)((w[k >> 2] >> (8 * (k & 3))) & 255u); }
-
-// Every pixel of this workgroup's chunk: f.px(R, G, B) per pixel, f.flush() after at most four of them.
-template <typename F>
-__device__ __forceinline__ void sn_each(const uint8_t* __restrict__ tiles, const sn_geom& g, F& f) {
-  const int tid = threadIdx.x;
-  const size_t n = blockIdx.x / g.chunks;
-  const long long p0 = (long long)(blockIdx.x % g.chunks) * g.chunk;
-  const long long left = g.HW - p0;
-  const int cnt = left < (long long)g.chunk ? (int)left : g.chunk;
-  const size_t HW = (size_t)g.HW;
-  const uint8_t* t = tiles + n * 3 * HW;
-  int done = 0;
-  if (g.vec) {
-    const int quads = cnt >> 2;
-    for (int q = tid; q < quads; q += 256) {
-      const size_t p = (size_t)p0 + 4 * (size_t)q;
-      uint32_t w[3];
-      if (g.planar) {
-        w[0] = *reinterpret_cast<const uint32_t*>(t + p);
-        w[1] = *reinterpret_cast<const uint32_t*>(t + HW + p);
-        w[2] = *reinterpret_cast<const uint32_t*>(t + 2 * HW + p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int c0 = sn_byte(w, j), c1 = sn_byte(w, 4 + j), c2 = sn_byte(w, 8 + j);
-          f.px(g.reverse ? c2 : c0, c1, g.reverse ? c0 : c2);
-        }
-      } else {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(t + 3 * p);
-        w[0] = src[0]; w[1] = src[1]; w[2] = src[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int c0 = sn_byte(w, 3 * j), c1 = sn_byte(w, 3 * j + 1), c2 = sn_byte(w, 3 * j + 2);
-          f.px(g.reverse ? c2 : c0, c1, g.reverse ? c0 : c2);
-        }
-      }
-      f.flush();
-    }
-    done = quads << 2;                               // planar: cnt % 4 == 0 here; interleaved: the last chunk may leave up to 3
-  }
-  for (int i = done + tid; i < cnt; i += 256) {
-    const size_t p = (size_t)p0 + (size_t)i;
-    int c0, c1, c2;
-    if (g.planar) {
-      c0 = t[p]; c1 = t[HW + p]; c2 = t[2 * HW + p];
-    } else {
-      c0 = t[3 * p]; c1 = t[3 * p + 1]; c2 = t[3 * p + 2];
-    }
-    f.px(g.reverse ? c2 : c0, c1, g.reverse ? c0 : c2);
-    f.flush();
-  }
-}
 
 __device__ __forceinline__ long long sn_wave_sum(long long v) {
 #pragma unroll
@@ -120,7 +60,7 @@ struct sn_moments_f {
 };
 
 __global__ __launch_bounds__(256) void sn_moments_kernel(const uint8_t* __restrict__ tiles, const int32_t* __restrict__ od_lut,
-                                                         int beta_q, unsigned long long* __restrict__ out, sn_geom g) {
+                                                         int beta_q, unsigned long long* __restrict__ out, u8px_geom g) {
   __shared__ int lut[256];
   __shared__ long long red[4][10];
   const int tid = threadIdx.x;
@@ -130,7 +70,7 @@ __global__ __launch_bounds__(256) void sn_moments_kernel(const uint8_t* __restri
   f.lut = lut; f.beta = beta_q;
 #pragma unroll
   for (int i = 0; i < 10; ++i) { f.q[i] = 0; f.acc[i] = 0; }
-  sn_each(tiles, g, f);
+  u8px_each(tiles, g, f);
 #pragma unroll
   for (int i = 0; i < 10; ++i) {
     const long long v = sn_wave_sum(f.acc[i]);
@@ -176,7 +116,7 @@ struct sn_angle_f {
 
 __global__ __launch_bounds__(256) void sn_angle_kernel(const uint8_t* __restrict__ tiles, const int32_t* __restrict__ od_lut, int beta_q,
                                                        sn_basis basis, const int32_t* __restrict__ dirs, int K,
-                                                       unsigned long long* __restrict__ hist, sn_geom g) {
+                                                       unsigned long long* __restrict__ hist, u8px_geom g) {
   __shared__ int lut[256];
   __shared__ int2 d[SN_KMAX];
   __shared__ unsigned h[SN_KMAX + 1];
@@ -187,7 +127,7 @@ __global__ __launch_bounds__(256) void sn_angle_kernel(const uint8_t* __restrict
   __syncthreads();
   sn_angle_f f;
   f.lut = lut; f.dirs = d; f.h = h; f.b = basis; f.beta = beta_q; f.K = K;
-  sn_each(tiles, g, f);
+  u8px_each(tiles, g, f);
   __syncthreads();
   for (int i = tid; i <= K; i += 256) {
     const unsigned v = h[i];
@@ -224,7 +164,7 @@ struct sn_conc_f {
 template <typename T>
 __global__ __launch_bounds__(256) void sn_conc_kernel(const uint8_t* __restrict__ tiles, const int32_t* __restrict__ od_lut,
                                                       sn_pinv<T> P, int qp, int csh, int bins, unsigned long long* __restrict__ hist,
-                                                      sn_geom g) {
+                                                      u8px_geom g) {
   __shared__ int lut[256];
   __shared__ unsigned h[2 * SN_BINSMAX];
   const int tid = threadIdx.x;
@@ -233,7 +173,7 @@ __global__ __launch_bounds__(256) void sn_conc_kernel(const uint8_t* __restrict_
   __syncthreads();
   sn_conc_f<T> f;
   f.lut = lut; f.h = h; f.P = P; f.qp = qp; f.csh = csh; f.bins = bins;
-  sn_each(tiles, g, f);
+  u8px_each(tiles, g, f);
   __syncthreads();
   for (int i = tid; i < 2 * bins; i += 256) {
     const unsigned v = h[i];
@@ -251,140 +191,61 @@ struct sn_apply_par {
   int qp, qs, shift, L, off;
 };
 
-// (c0, c1, c2) as stored -> the normalised bytes, in the same stored order
+// px: the normalised bytes of one pixel, in place of its R, G, B
 template <typename T>
-__device__ __forceinline__ void sn_norm(const int* lut, const uint8_t* olut, const sn_apply_par<T>& a, int reverse, int& c0, int& c1,
-                                        int& c2) {
-  const int oR = lut[reverse ? c2 : c0], oG = lut[c1], oB = lut[reverse ? c0 : c2];
-  long long k[2];
+struct sn_apply_f {
+  const int* lut;
+  const uint8_t* olut;
+  const sn_apply_par<T>& a;
+  __device__ __forceinline__ void px(int& R, int& G, int& B) {
+    const int oR = lut[R], oG = lut[G], oB = lut[B];
+    long long k[2];
 #pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const long long conc = sn_conc(a.P, s, oR, oG, oB, a.qp);
-    // T = int: the host has checked that conc and conc2 fit int32, so the casts below drop nothing
-    k[s] = ((long long)(T)conc * (long long)a.scale[s]) >> a.qs;
-  }
-  int o[3];
+    for (int s = 0; s < 2; ++s) {
+      const long long conc = sn_conc(a.P, s, oR, oG, oB, a.qp);
+      // T = int: the host has checked that conc and conc2 fit int32, so the casts below drop nothing
+      k[s] = ((long long)(T)conc * (long long)a.scale[s]) >> a.qs;
+    }
+    int o[3];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    long long v = ((long long)a.href[2 * c] * (long long)(T)k[0] + (long long)a.href[2 * c + 1] * (long long)(T)k[1] + a.rnd) >> a.shift;
-    v += a.off;
-    v = v < 0 ? 0 : (v > (long long)(a.L - 1) ? (long long)(a.L - 1) : v);
-    o[c] = olut[(int)v];
+    for (int c = 0; c < 3; ++c) {
+      long long v = ((long long)a.href[2 * c] * (long long)(T)k[0] + (long long)a.href[2 * c + 1] * (long long)(T)k[1] + a.rnd) >> a.shift;
+      v += a.off;
+      v = v < 0 ? 0 : (v > (long long)(a.L - 1) ? (long long)(a.L - 1) : v);
+      o[c] = olut[(int)v];
+    }
+    R = o[0]; G = o[1]; B = o[2];
   }
-  c0 = reverse ? o[2] : o[0];
-  c1 = o[1];
-  c2 = reverse ? o[0] : o[2];
-}
+  __device__ __forceinline__ void flush() {}
+};
 
 // src and dst are NOT restrict: dst == src is the in-place call.  A lane reads all the bytes of its pixels before it writes any of
-// them, and no other lane touches those bytes.
+// them, and no other lane touches those bytes (u8px_map, rg_u8px.h).
 template <typename T>
 __global__ __launch_bounds__(256) void sn_apply_kernel(const uint8_t* src, uint8_t* dst, const int32_t* __restrict__ od_lut,
-                                                       const uint8_t* __restrict__ out_lut, sn_apply_par<T> a, sn_geom g) {
+                                                       const uint8_t* __restrict__ out_lut, sn_apply_par<T> a, u8px_geom g) {
   __shared__ int lut[256];
   __shared__ uint8_t olut[SN_LMAX];
   const int tid = threadIdx.x;
   lut[tid] = od_lut[tid];
   for (int i = tid; i < a.L; i += 256) olut[i] = out_lut[i];
   __syncthreads();
-  const size_t n = blockIdx.x / g.chunks;
-  const long long p0 = (long long)(blockIdx.x % g.chunks) * g.chunk;
-  const long long left = g.HW - p0;
-  const int cnt = left < (long long)g.chunk ? (int)left : g.chunk;
-  const size_t HW = (size_t)g.HW;
-  const uint8_t* t = src + n * 3 * HW;
-  uint8_t* u = dst + n * 3 * HW;
-  int done = 0;
-  if (g.vec) {
-    const int quads = cnt >> 2;
-    for (int q = tid; q < quads; q += 256) {
-      const size_t p = (size_t)p0 + 4 * (size_t)q;
-      uint32_t w[3], r[3] = {0u, 0u, 0u};
-      if (g.planar) {
-        w[0] = *reinterpret_cast<const uint32_t*>(t + p);
-        w[1] = *reinterpret_cast<const uint32_t*>(t + HW + p);
-        w[2] = *reinterpret_cast<const uint32_t*>(t + 2 * HW + p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          int c0 = sn_byte(w, j), c1 = sn_byte(w, 4 + j), c2 = sn_byte(w, 8 + j);
-          sn_norm(lut, olut, a, g.reverse, c0, c1, c2);
-          r[0] |= (uint32_t)c0 << (8 * j);
-          r[1] |= (uint32_t)c1 << (8 * j);
-          r[2] |= (uint32_t)c2 << (8 * j);
-        }
-        *reinterpret_cast<uint32_t*>(u + p) = r[0];
-        *reinterpret_cast<uint32_t*>(u + HW + p) = r[1];
-        *reinterpret_cast<uint32_t*>(u + 2 * HW + p) = r[2];
-      } else {
-        const uint32_t* s4 = reinterpret_cast<const uint32_t*>(t + 3 * p);
-        w[0] = s4[0]; w[1] = s4[1]; w[2] = s4[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          int c0 = sn_byte(w, 3 * j), c1 = sn_byte(w, 3 * j + 1), c2 = sn_byte(w, 3 * j + 2);
-          sn_norm(lut, olut, a, g.reverse, c0, c1, c2);
-          const int k0 = 3 * j, k1 = 3 * j + 1, k2 = 3 * j + 2;
-          r[k0 >> 2] |= (uint32_t)c0 << (8 * (k0 & 3));
-          r[k1 >> 2] |= (uint32_t)c1 << (8 * (k1 & 3));
-          r[k2 >> 2] |= (uint32_t)c2 << (8 * (k2 & 3));
-        }
-        uint32_t* d4 = reinterpret_cast<uint32_t*>(u + 3 * p);
-        d4[0] = r[0]; d4[1] = r[1]; d4[2] = r[2];
-      }
-    }
-    done = quads << 2;
-  }
-  for (int i = done + tid; i < cnt; i += 256) {
-    const size_t p = (size_t)p0 + (size_t)i;
-    int c0, c1, c2;
-    if (g.planar) {
-      c0 = t[p]; c1 = t[HW + p]; c2 = t[2 * HW + p];
-    } else {
-      c0 = t[3 * p]; c1 = t[3 * p + 1]; c2 = t[3 * p + 2];
-    }
-    sn_norm(lut, olut, a, g.reverse, c0, c1, c2);
-    if (g.planar) {
-      u[p] = (uint8_t)c0; u[HW + p] = (uint8_t)c1; u[2 * HW + p] = (uint8_t)c2;
-    } else {
-      u[3 * p] = (uint8_t)c0; u[3 * p + 1] = (uint8_t)c1; u[3 * p + 2] = (uint8_t)c2;
-    }
-  }
+  sn_apply_f<T> f = {lut, olut, a};
+  u8px_map(src, dst, g, f);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// what the four entry points share: shape, flags, limits, the launch geometry.  *blocks = 0 for N == 0.
+// what the four entry points share: the two buffers every pass reads, the launch geometry, the limit of a call.  *blocks = 0 for
+// N == 0.  accumulate == 0: the output is zeroed by u8px_zero in front of the counting kernel.
 int sn_plan(const char* what, const void* tiles, int N, int H, int W, int flags, const void* od_lut, int chunk, bool aligned,
-            sn_geom* g, unsigned* blocks) {
+            u8px_geom* g, unsigned* blocks) {
   RG_REQUIRE(tiles && od_lut, RG_EINVAL, "%s: NULL buffer", what);
-  RG_REQUIRE(N >= 0 && H > 0 && W > 0, RG_EINVAL, "%s: bad shape N %d H %d W %d", what, N, H, W);
-  RG_REQUIRE((flags & ~(RG_EXPORT_PLANAR | RG_EXPORT_REVERSE)) == 0, RG_EINVAL, "%s: unknown flag bits 0x%x", what, flags);
-  RG_REQUIRE(((uintptr_t)od_lut & 3) == 0, RG_EINVAL, "%s: od_lut needs 4-byte alignment", what);
-  const long long HW = (long long)H * W;                     // < 2^62
-  RG_REQUIRE(HW <= SN_MAXPIX && (N == 0 || (long long)N <= SN_MAXPIX / HW), RG_EUNSUPPORTED,
+  const long long HW = (long long)H * W;                     // a bad shape is u8px_plan's to refuse
+  RG_REQUIRE(N < 0 || H <= 0 || W <= 0 || (HW <= SN_MAXPIX && (N == 0 || (long long)N <= SN_MAXPIX / HW)), RG_EUNSUPPORTED,
              "%s: N %d H %d W %d is more than 2^33 pixels per call", what, N, H, W);
-  const int planar = (flags & RG_EXPORT_PLANAR) != 0;
-  g->planar = planar;
-  g->reverse = (flags & RG_EXPORT_REVERSE) != 0;
-  g->chunk = chunk;
-  g->HW = planar ? HW : HW * N;                              // interleaved: one stream of pixels
-  const long long per = (g->HW + chunk - 1) / chunk;        // <= 2^33 / 8192
-  const long long total = planar ? per * N : per;
-  RG_REQUIRE(total <= 0x7fffffffLL, RG_EUNSUPPORTED, "%s: N %d H %d W %d is more than 2^31 - 1 workgroups", what, N, H, W);
-  g->chunks = (unsigned)(per > 0 ? per : 1);
-  g->vec = aligned && (!planar || HW % 4 == 0);
-  *blocks = (unsigned)total;
-  return RG_OK;
-}
-
-// accumulate == 0: the output is zeroed by a kernel in front of the counting one (as tq_zero_kernel of rg_tissue.hip: a captured
-// call is then a plain chain of kernel nodes).  words <= 2 * SN_BINSMAX.
-__global__ __launch_bounds__(256) void sn_zero_kernel(unsigned long long* __restrict__ p, int words) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < words) p[i] = 0ull;
-}
-
-int sn_zero(const char* what, void* p, int words, hipStream_t st) {
-  hipLaunchKernelGGL(sn_zero_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, (unsigned long long*)p, words);
-  RG_LAUNCH_CHECK(what);
+  const int rc = u8px_plan(what, N, H, W, flags, chunk, aligned, false, g, blocks);
+  if (rc != RG_OK) return rc;
+  RG_REQUIRE(((uintptr_t)od_lut & 3) == 0, RG_EINVAL, "%s: od_lut needs 4-byte alignment", what);
   return RG_OK;
 }
 
@@ -397,7 +258,7 @@ constexpr long long SN_PMAX = 1LL << 40;                      // on |pinv6[i]|: 
 
 extern "C" int rg_stain_moments(const uint8_t* tiles, int N, int H, int W, int flags, const int32_t* od_lut, int beta_q, int64_t* out,
                                 int accumulate, void* stream) {
-  sn_geom g;
+  u8px_geom g;
   unsigned blocks;
   RG_REQUIRE(out, RG_EINVAL, "stain_moments: NULL buffer");
   int rc = sn_plan("stain_moments", tiles, N, H, W, flags, od_lut, SN_CHUNK, ((uintptr_t)tiles & 3) == 0, &g, &blocks);
@@ -405,7 +266,7 @@ extern "C" int rg_stain_moments(const uint8_t* tiles, int N, int H, int W, int f
   RG_REQUIRE(((uintptr_t)out & 7) == 0, RG_EINVAL, "stain_moments: out needs 8-byte alignment");
   if (N == 0) return RG_OK;
   hipStream_t st = rg_stream(stream);
-  if (!accumulate && (rc = sn_zero("stain_moments", out, 10, st)) != RG_OK) return rc;
+  if (!accumulate && (rc = u8px_zero("stain_moments", out, 2 * 10, st)) != RG_OK) return rc;
   hipLaunchKernelGGL(sn_moments_kernel, dim3(blocks), dim3(256), 0, st, tiles, od_lut, beta_q, (unsigned long long*)out, g);
   RG_LAUNCH_CHECK("stain_moments");
   return RG_OK;
@@ -413,7 +274,7 @@ extern "C" int rg_stain_moments(const uint8_t* tiles, int N, int H, int W, int f
 
 extern "C" int rg_stain_angle_hist(const uint8_t* tiles, int N, int H, int W, int flags, const int32_t* od_lut, int beta_q,
                                    const int* basis6, const int32_t* dirs, int K, uint64_t* hist, int accumulate, void* stream) {
-  sn_geom g;
+  u8px_geom g;
   unsigned blocks;
   RG_REQUIRE(basis6 && dirs && hist, RG_EINVAL, "stain_angle_hist: NULL buffer");
   int rc = sn_plan("stain_angle_hist", tiles, N, H, W, flags, od_lut, SN_CHUNK, ((uintptr_t)tiles & 3) == 0, &g, &blocks);
@@ -428,7 +289,7 @@ extern "C" int rg_stain_angle_hist(const uint8_t* tiles, int N, int H, int W, in
   }
   if (N == 0) return RG_OK;
   hipStream_t st = rg_stream(stream);
-  if (!accumulate && (rc = sn_zero("stain_angle_hist", hist, K + 1, st)) != RG_OK) return rc;
+  if (!accumulate && (rc = u8px_zero("stain_angle_hist", hist, 2 * (size_t)(K + 1), st)) != RG_OK) return rc;
   hipLaunchKernelGGL(sn_angle_kernel, dim3(blocks), dim3(256), 0, st, tiles, od_lut, beta_q, b, dirs, K, (unsigned long long*)hist, g);
   RG_LAUNCH_CHECK("stain_angle_hist");
   return RG_OK;
@@ -436,7 +297,7 @@ extern "C" int rg_stain_angle_hist(const uint8_t* tiles, int N, int H, int W, in
 
 extern "C" int rg_stain_conc_hist(const uint8_t* tiles, int N, int H, int W, int flags, const int32_t* od_lut, const long long* pinv6,
                                   int qp, int csh, int bins, uint64_t* hist, int accumulate, void* stream) {
-  sn_geom g;
+  u8px_geom g;
   unsigned blocks;
   RG_REQUIRE(pinv6 && hist, RG_EINVAL, "stain_conc_hist: NULL buffer");
   int rc = sn_plan("stain_conc_hist", tiles, N, H, W, flags, od_lut, SN_CHUNK, ((uintptr_t)tiles & 3) == 0, &g, &blocks);
@@ -451,7 +312,7 @@ extern "C" int rg_stain_conc_hist(const uint8_t* tiles, int N, int H, int W, int
   }
   if (N == 0) return RG_OK;
   hipStream_t st = rg_stream(stream);
-  if (!accumulate && (rc = sn_zero("stain_conc_hist", hist, 2 * bins, st)) != RG_OK) return rc;
+  if (!accumulate && (rc = u8px_zero("stain_conc_hist", hist, 2 * (size_t)(2 * bins), st)) != RG_OK) return rc;
   if (narrow) {
     sn_pinv<int> P;
     for (int i = 0; i < 6; ++i) P.p[i] = (int)pinv6[i];
@@ -469,7 +330,7 @@ extern "C" int rg_stain_conc_hist(const uint8_t* tiles, int N, int H, int W, int
 extern "C" int rg_stain_apply(const uint8_t* src, uint8_t* dst, int N, int H, int W, int flags, const int32_t* od_lut,
                               const long long* pinv6, int qp, const long long* scale2, int qs, const int* href6, int shift,
                               const uint8_t* out_lut, int L, int off, void* stream) {
-  sn_geom g;
+  u8px_geom g;
   unsigned blocks;
   RG_REQUIRE(dst && pinv6 && scale2 && href6 && out_lut, RG_EINVAL, "stain_apply: NULL buffer");
   int rc = sn_plan("stain_apply", src, N, H, W, flags, od_lut, SN_APPLY_CHUNK, (((uintptr_t)src | (uintptr_t)dst) & 3) == 0, &g, &blocks);

@@ -4,9 +4,9 @@
 // fractions, percentile interpolation, low contrast -- are the caller's (rna_gan_amd/tissue.py).
 //
 // Five launches on the caller's stream; the tile bytes are read from memory TWICE (plus the dilation halo):
-//   tq_zero       the per-tile workspace (TQ_WORDS counters per tile), with dword stores (a kernel, not a memset node: the launches
-//                 of a captured call then form one plain chain of kernel nodes)
-//   tq_hist       read 1: a workgroup owns TQ_CHUNK consecutive pixels of one tile.  Five LDS histograms (R, G, B, s8: 256 bins each;
+//   u8px_zero     the per-tile workspace (TQ_WORDS counters per tile)
+//   tq_hist       read 1: a workgroup owns TQ_CHUNK consecutive pixels of one tile, read through the pixel stream of rg_u8px.h.
+//                 Five LDS histograms (R, G, B, s8: 256 bins each;
 //                 the luma's coarse level L >> 10: 2491 of TQ_COARSE bins) filled with LDS atomics, merged into the tile's counters
 //                 with one global 32-bit integer atomic per OCCUPIED bin.
 //   tq_scan       one workgroup per tile, wave c = channel c: Otsu on the merged histogram (integer prefix sums in LDS, the 255
@@ -21,7 +21,7 @@
 //   tq_final      one workgroup per tile: the fine bin of each rank; writes the tile's 12 stats words with plain stores.
 // s8 takes no division: a 256-entry table of ceil(2^24 / mx) in LDS and one 32 x 32 -> 64-bit multiply (tq_s8).
 // Integer atomics commute, so no result depends on the launch plan, on N or on a neighbouring tile; no 16-bit type is involved.
-#include "rg_common.h"
+#include "rg_u8px.h"
 
 #pragma clang fp contract(off)
 
@@ -57,80 +57,34 @@ __device__ __forceinline__ int tq_s8(const unsigned* inv, int R, int G, int B) {
 }
 __device__ __forceinline__ int tq_luma(int R, int G, int B) { return 2125 * R + 7154 * G + 721 * B; }
 
-// pixel p of the tile at t (HW pixels)
-__device__ __forceinline__ void tq_load(const uint8_t* __restrict__ t, size_t HW, size_t p, int planar, int reverse, int& R, int& G,
-                                        int& B) {
-  int c0, c2;
-  if (planar) {
-    c0 = t[p]; G = t[HW + p]; c2 = t[2 * HW + p];
-  } else {
-    c0 = t[3 * p]; G = t[3 * p + 1]; c2 = t[3 * p + 2];
-  }
-  R = reverse ? c2 : c0;
-  B = reverse ? c0 : c2;
-}
-
-// a grid-stride fill: the caller launches at most 2^20 workgroups whatever `words` is
-__global__ __launch_bounds__(256) void tq_zero_kernel(unsigned* __restrict__ ws, size_t words) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) ws[i] = 0u;
-}
-
 struct tq_hist_lds {
   unsigned h[4][256];
   unsigned coarse[TQ_COARSE];
   unsigned inv[256];
 };
 
-__device__ __forceinline__ void tq_count(tq_hist_lds& s, int c0, int G, int c2, int reverse) {
-  const int R = reverse ? c2 : c0, B = reverse ? c0 : c2;
-  atomicAdd(&s.h[0][R], 1u);
-  atomicAdd(&s.h[1][G], 1u);
-  atomicAdd(&s.h[2][B], 1u);
-  atomicAdd(&s.h[3][tq_s8(s.inv, R, G, B)], 1u);
-  atomicAdd(&s.coarse[tq_luma(R, G, B) >> 10], 1u);
-}
+struct tq_count_f {
+  tq_hist_lds& s;
+  __device__ __forceinline__ void px(int R, int G, int B) {
+    atomicAdd(&s.h[0][R], 1u);
+    atomicAdd(&s.h[1][G], 1u);
+    atomicAdd(&s.h[2][B], 1u);
+    atomicAdd(&s.h[3][tq_s8(s.inv, R, G, B)], 1u);
+    atomicAdd(&s.coarse[tq_luma(R, G, B) >> 10], 1u);
+  }
+  __device__ __forceinline__ void flush() {}
+};
 
-__device__ __forceinline__ int tq_byte(const uint32_t* w, int k) { return (int)((w[k >> 2] >> (8 * (k & 3))) & 255u); }
-
-// grid: N * chunks workgroups; workgroup b: tile b / chunks, pixels [(b % chunks) * TQ_CHUNK, + TQ_CHUNK) of it.
-// vec: tiles is 4-byte aligned and HW % 4 == 0 (every tile, plane and chunk then starts on a dword): a lane takes 4 pixels from
-// three dword loads
-__global__ __launch_bounds__(256) void tq_hist_kernel(const uint8_t* __restrict__ tiles, unsigned* __restrict__ ws, int HW, int chunks,
-                                                      int planar, int reverse, int vec) {
+// grid: N * geom.chunks workgroups, every tile chunked on its own (u8px_plan's per_tile): workgroup b counts into tile b / chunks
+__global__ __launch_bounds__(256) void tq_hist_kernel(const uint8_t* __restrict__ tiles, unsigned* __restrict__ ws, u8px_geom geom) {
   __shared__ tq_hist_lds s;
   const int tid = threadIdx.x;
-  const size_t n = blockIdx.x / (unsigned)chunks;
-  const int p0 = (int)(blockIdx.x % (unsigned)chunks) * TQ_CHUNK;
-  const int cnt = min(TQ_CHUNK, HW - p0);
+  const size_t n = blockIdx.x / geom.chunks;
   for (int i = tid; i < 4 * 256 + TQ_COARSE; i += 256) (&s.h[0][0])[i] = 0u;      // h and coarse are contiguous
   tq_fill_inv(s.inv, tid);
   __syncthreads();
-  const uint8_t* t = tiles + n * 3 * (size_t)HW;
-  if (vec) {
-    const int quads = cnt >> 2;                                                    // cnt % 4 == 0 here
-    for (int q = tid; q < quads; q += 256) {
-      const size_t p = (size_t)p0 + 4 * (size_t)q;
-      uint32_t w[3];
-      if (planar) {
-        w[0] = *reinterpret_cast<const uint32_t*>(t + p);
-        w[1] = *reinterpret_cast<const uint32_t*>(t + (size_t)HW + p);
-        w[2] = *reinterpret_cast<const uint32_t*>(t + 2 * (size_t)HW + p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tq_count(s, tq_byte(w, j), tq_byte(w, 4 + j), tq_byte(w, 8 + j), reverse);
-      } else {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(t + 3 * p);
-        w[0] = src[0]; w[1] = src[1]; w[2] = src[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tq_count(s, tq_byte(w, 3 * j), tq_byte(w, 3 * j + 1), tq_byte(w, 3 * j + 2), reverse);
-      }
-    }
-  } else {
-    for (int i = tid; i < cnt; i += 256) {
-      int R, G, B;
-      tq_load(t, (size_t)HW, (size_t)p0 + i, planar, 0, R, G, B);
-      tq_count(s, R, G, B, reverse);
-    }
-  }
+  tq_count_f f = {s};
+  u8px_each(tiles, geom, f);
   __syncthreads();
   unsigned* g = ws + n * TQ_WORDS;                // TQ_OFF_HIST = 0 and TQ_OFF_COARSE = 1024: the same contiguous order as in LDS
   for (int i = tid; i < 4 * 256 + TQ_COARSE; i += 256) {
@@ -272,7 +226,7 @@ __global__ __launch_bounds__(256) void tq_mask_kernel(const uint8_t* __restrict_
       const int rr = (int)(((unsigned)i * rwinv) >> 20), cc = i - rr * RW;
       const int gr = r0 - d + rr, gc = c0g - d + cc;
       c0[j] = -1;
-      if (i < total && gr >= 0 && gr < H && gc >= 0 && gc < W) tq_load(t, HW, (size_t)gr * W + gc, planar, 0, c0[j], c1[j], c2[j]);
+      if (i < total && gr >= 0 && gr < H && gc >= 0 && gc < W) u8px_load(t, HW, (size_t)gr * W + gc, planar, 0, c0[j], c1[j], c2[j]);
     }
 #pragma unroll
     for (int j = 0; j < TQ_BATCH; ++j) {
@@ -370,9 +324,12 @@ extern "C" size_t rg_tile_qc_workspace_bytes(int N, int H, int W) {
 extern "C" int rg_tile_qc(const uint8_t* tiles, int N, int H, int W, int flags, int rgb_min, int dilate, const int* ranks4,
                           int32_t* stats, uint8_t* mask_or_null, void* workspace, size_t workspace_bytes, void* stream) {
   RG_REQUIRE(tiles && stats && ranks4 && workspace, RG_EINVAL, "tile_qc: NULL buffer");
-  RG_REQUIRE(N >= 0 && H > 0 && W > 0, RG_EINVAL, "tile_qc: bad shape N %d H %d W %d", N, H, W);
-  RG_REQUIRE((long long)H * W <= (1LL << 26), RG_EUNSUPPORTED, "tile_qc: H %d W %d is more than 2^26 pixels per tile", H, W);
-  RG_REQUIRE((flags & ~(RG_EXPORT_PLANAR | RG_EXPORT_REVERSE)) == 0, RG_EINVAL, "tile_qc: unknown flag bits 0x%x", flags);
+  // (a bad shape is u8px_plan's to refuse)
+  RG_REQUIRE(N < 0 || H <= 0 || W <= 0 || (long long)H * W <= (1LL << 26), RG_EUNSUPPORTED, "tile_qc: H %d W %d is more than 2^26 pixels per tile", H, W);
+  u8px_geom geom;
+  unsigned hist_blocks;
+  int rc = u8px_plan("tile_qc", N, H, W, flags, TQ_CHUNK, ((uintptr_t)tiles & 3) == 0, true, &geom, &hist_blocks);
+  if (rc != RG_OK) return rc;
   RG_REQUIRE(rgb_min >= 0 && rgb_min <= 255, RG_EINVAL, "tile_qc: rgb_min %d is not in 0..255", rgb_min);
   RG_REQUIRE(dilate >= 0 && dilate <= TQ_DMAX, RG_EINVAL, "tile_qc: dilate %d is not in 0..%d", dilate, TQ_DMAX);
   const int HW = H * W;
@@ -385,22 +342,15 @@ extern "C" int rg_tile_qc(const uint8_t* tiles, int N, int H, int W, int flags, 
   if (N == 0) return RG_OK;
   const size_t need = (size_t)N * TQ_WORDS * sizeof(unsigned);
   RG_REQUIRE(workspace_bytes >= need, RG_EINVAL, "tile_qc: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-  const int chunks = (HW + TQ_CHUNK - 1) / TQ_CHUNK;
   const int bx = (W + TQ_TW - 1) / TQ_TW, by = (H + TQ_TH - 1) / TQ_TH;
-  const long long limit = 0x7fffffffLL;
-  RG_REQUIRE((long long)N * chunks <= limit && (long long)N * bx * by <= limit, RG_EUNSUPPORTED,
-             "tile_qc: N %d H %d W %d is more than 2^31 - 1 workgroups", N, H, W);
-  const int planar = (flags & RG_EXPORT_PLANAR) != 0, reverse = (flags & RG_EXPORT_REVERSE) != 0;
-  const int vec = ((uintptr_t)tiles & 3) == 0 && HW % 4 == 0;
+  RG_REQUIRE((long long)N * bx * by <= 0x7fffffffLL, RG_EUNSUPPORTED, "tile_qc: N %d H %d W %d is more than 2^31 - 1 workgroups", N, H, W);
   hipStream_t st = rg_stream(stream);
   unsigned* ws = (unsigned*)workspace;
-  const size_t words = (size_t)N * TQ_WORDS;
-  const size_t zblocks = (words + 4 * 256 - 1) / (4 * 256);                         // four dwords per lane, at most 2^20 workgroups
-  hipLaunchKernelGGL(tq_zero_kernel, dim3((unsigned)(zblocks < (1u << 20) ? zblocks : (1u << 20))), dim3(256), 0, st, ws, words);
-  hipLaunchKernelGGL(tq_hist_kernel, dim3((unsigned)(N * chunks)), dim3(256), 0, st, tiles, ws, HW, chunks, planar, reverse, vec);
+  if ((rc = u8px_zero("tile_qc", ws, (size_t)N * TQ_WORDS, st)) != RG_OK) return rc;
+  hipLaunchKernelGGL(tq_hist_kernel, dim3(hist_blocks), dim3(256), 0, st, tiles, ws, geom);
   hipLaunchKernelGGL(tq_scan_kernel, dim3((unsigned)N), dim3(256), 0, st, ws, ranks);
-  hipLaunchKernelGGL(tq_mask_kernel, dim3((unsigned)(N * bx * by)), dim3(256), 0, st, tiles, ws, mask_or_null, H, W, bx, by, planar,
-                     reverse, rgb_min, dilate);
+  hipLaunchKernelGGL(tq_mask_kernel, dim3((unsigned)(N * bx * by)), dim3(256), 0, st, tiles, ws, mask_or_null, H, W, bx, by, geom.planar,
+                     geom.reverse, rgb_min, dilate);
   hipLaunchKernelGGL(tq_final_kernel, dim3((unsigned)N), dim3(256), 0, st, (const unsigned*)ws, stats);
   RG_LAUNCH_CHECK("tile_qc");
   return RG_OK;

@@ -44,6 +44,29 @@ def export_flags(layout="nhwc", order="rgb", rounding="round"):
         (RG_EXPORT_TRUNC if rounding == "trunc" else 0)
 
 
+def tile_args(tiles, layout, order, what):
+    """(N, H, W) of uint8 tiles, (N, H, W, 3) ("nhwc") or (N, 3, H, W) ("nchw"), as the image-side functions take them; ``what``
+    names the caller in the messages"""
+    export_flags(layout, order)
+    if not torch.is_tensor(tiles) or tiles.dim() != 4 or tiles.dtype != torch.uint8:
+        raise ValueError("%s takes a uint8 (N, H, W, 3) or (N, 3, H, W) tensor" % what)
+    if tiles.shape[3 if layout == "nhwc" else 1] != 3:
+        raise ValueError("%s needs 3 channels in layout %s, got %s" % (what, layout, tuple(tiles.shape)))
+    N = tiles.shape[0]
+    H, W = (tiles.shape[1], tiles.shape[2]) if layout == "nhwc" else (tiles.shape[2], tiles.shape[3])
+    return N, H, W
+
+
+def rgb_numpy(tiles, layout, order):
+    """a CPU tensor as (N, H, W, 3) numpy in R, G, B order (a view where possible)"""
+    a = tiles.numpy()
+    if layout == "nchw":
+        a = a.transpose(0, 2, 3, 1)
+    if order == "bgr":
+        a = a[..., ::-1]
+    return a
+
+
 def _out_shape(shape, layout):
     N, C, H, W = shape
     return (N, H, W, C) if layout == "nhwc" else (N, C, H, W)
@@ -82,9 +105,7 @@ def tiles_u8(images, layout="nhwc", order="rgb", rounding="round", sub=-1.0, div
         out.copy_(b.permute(0, 2, 3, 1) if layout == "nhwc" else b)
         return out
     src = images.contiguous()
-    with torch.cuda.device(src.device):
-        _abi.check(_abi.load().rg_tile_export_u8(src.data_ptr(), out.data_ptr(), N, C, H, W, sub, div, flags,
-                                                 torch.cuda.current_stream(src.device).cuda_stream), "rg_tile_export_u8")
+    _abi.launch("rg_tile_export_u8", src.device, src.data_ptr(), out.data_ptr(), N, C, H, W, sub, div, flags)
     return out
 
 

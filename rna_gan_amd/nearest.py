@@ -64,9 +64,7 @@ def _descriptors_into(tiles_u8, factor, desc, norm2):
         desc[:, :D] = v.reshape(N, D).to(torch.int8)
         norm2.copy_((v * v).sum(dim=(1, 2, 3)).to(torch.int32))
         return
-    with torch.cuda.device(tiles_u8.device):
-        _abi.check(_abi.load().rg_tile_descriptor_i8(tiles_u8.data_ptr(), N, C, S, factor, desc.data_ptr(), ldd, norm2.data_ptr(),
-                                                     torch.cuda.current_stream(tiles_u8.device).cuda_stream), "rg_tile_descriptor_i8")
+    _abi.launch("rg_tile_descriptor_i8", tiles_u8.device, tiles_u8.data_ptr(), N, C, S, factor, desc.data_ptr(), ldd, norm2.data_ptr())
 
 
 def descriptors(tiles_u8, factor=4):
@@ -131,14 +129,11 @@ def nearest(query_desc, ref_desc, k=4, exclude=None):
                 key = torch.where(rows[None, :] == exclude[i:i + 256].long()[:, None], torch.iinfo(torch.int64).max, key)
             keys[i:i + 256] = torch.topk(key, k, dim=1, largest=False, sorted=True).values
     else:
-        lib = _abi.load()
-        need = lib.rg_nn_topk_ws_bytes(Q, N, k)
+        need = _abi.load().rg_nn_topk_ws_bytes(Q, N, k)
         ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=a.device)
         keys = torch.empty((Q, k), dtype=torch.int64, device=a.device)          # the uint64 keys are below 2^63
-        with torch.cuda.device(a.device):
-            _abi.check(lib.rg_nn_topk_i8(a.data_ptr(), na.data_ptr(), Q, b.data_ptr(), nb.data_ptr(), N, ldd, ldd, k,
-                                         0 if exclude is None else exclude.data_ptr(), keys.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         torch.cuda.current_stream(a.device).cuda_stream), "rg_nn_topk_i8")
+        _abi.launch("rg_nn_topk_i8", a.device, a.data_ptr(), na.data_ptr(), Q, b.data_ptr(), nb.data_ptr(), N, ldd, ldd, k,
+                    0 if exclude is None else exclude.data_ptr(), keys.data_ptr(), ws.data_ptr(), ws.numel())
     return keys >> 32, keys & 0xffffffff
 
 

@@ -267,10 +267,8 @@ class DeviceTileLoader:
                 return x
             return torch.stack([d4_apply(x[k], c) for k, c in enumerate(codes.tolist())]).contiguous()
         out = torch.empty((n, C, S, S), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _abi.check(_abi.load().rg_tile_gather_transform(
-                ts.tiles.data_ptr(), M, index.data_ptr(), out.data_ptr(), n, C, S, 0 if codes is None else codes.data_ptr(),
-                self.mean, self.std, torch.cuda.current_stream(device).cuda_stream), "rg_tile_gather_transform")
+        _abi.launch("rg_tile_gather_transform", device, ts.tiles.data_ptr(), M, index.data_ptr(), out.data_ptr(), n, C, S,
+                    0 if codes is None else codes.data_ptr(), self.mean, self.std)
         return out
 
     def __iter__(self):

@@ -300,10 +300,8 @@ def rows_gather(rows, index, n=None, ld_dst=None):
     out = torch.empty((int(n), ld), dtype=torch.float32, device=rows.device)
     if int(n) == 0:
         return out                       # (an empty tensor has no address to hand over)
-    with torch.cuda.device(rows.device):
-        _abi.check(_abi.load().rg_rows_gather_f32(rows.data_ptr(), M, F, F, 0 if index is None else index.data_ptr(),
-                                                  out.data_ptr(), int(n), ld,
-                                                  torch.cuda.current_stream(rows.device).cuda_stream), "rg_rows_gather_f32")
+    _abi.launch("rg_rows_gather_f32", rows.device, rows.data_ptr(), M, F, F, 0 if index is None else index.data_ptr(), out.data_ptr(),
+                int(n), ld)
     return out
 
 

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .export import LAYOUTS, ORDERS, RG_EXPORT_PLANAR, RG_EXPORT_REVERSE
+from .export import export_flags, rgb_numpy, tile_args
 
 IO = 240
 BETA = 0.15
@@ -286,34 +286,11 @@ def _apply_numpy(rgb, pinv6, scale2, href6):
 
 
 # ------------------------------------------------------------------ arguments and the device calls
-def _check(tiles, layout, order, what):
-    if layout not in LAYOUTS:
-        raise ValueError("layout must be one of %s" % (LAYOUTS,))
-    if order not in ORDERS:
-        raise ValueError("order must be one of %s" % (ORDERS,))
-    if not torch.is_tensor(tiles) or tiles.dim() != 4 or tiles.dtype != torch.uint8:
-        raise ValueError("%s takes a uint8 (N, H, W, 3) or (N, 3, H, W) tensor" % what)
-    if tiles.shape[3 if layout == "nhwc" else 1] != 3:
-        raise ValueError("%s needs 3 channels in layout %s, got %s" % (what, layout, tuple(tiles.shape)))
-    N = tiles.shape[0]
-    H, W = (tiles.shape[1], tiles.shape[2]) if layout == "nhwc" else (tiles.shape[2], tiles.shape[3])
+def _tile_args(tiles, layout, order, what):
+    N, H, W = tile_args(tiles, layout, order, what)
     if H < 1 or W < 1:
         raise ValueError("%s needs H, W >= 1" % what)
     return N, H, W
-
-
-def _rgb_numpy(tiles, layout, order):
-    """a CPU tensor as (N, H, W, 3) numpy in R, G, B order (a view where possible)"""
-    a = tiles.numpy()
-    if layout == "nchw":
-        a = a.transpose(0, 2, 3, 1)
-    if order == "bgr":
-        a = a[..., ::-1]
-    return a
-
-
-def _flags(layout, order):
-    return (RG_EXPORT_PLANAR if layout == "nchw" else 0) | (RG_EXPORT_REVERSE if order == "bgr" else 0)
 
 
 def _pieces(N, H, W, batch):
@@ -338,7 +315,7 @@ class _Device:
 
     @classmethod
     def get(cls, dev):
-        key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+        key = _abi.device_key(dev)
         if key not in cls._cache:
             cls._cache[key] = cls(dev)
         return cls._cache[key]
@@ -352,42 +329,34 @@ def _ii(values):
     return (ctypes.c_int * len(values))(*values)
 
 
-def _ptr(a):
-    return ctypes.cast(a, ctypes.c_void_p)
-
-
 # ------------------------------------------------------------------ the public functions
 def fit(tiles, layout="nhwc", order="rgb", batch=None):
     """uint8 tiles, (N, H, W, 3) ("nhwc") or (N, 3, H, W) ("nchw"), stored R, G, B ("rgb") or B, G, R ("bgr"), fitted TOGETHER as one
     set -> StainFit.  On a CUDA tensor: three launches on the current stream (rg_stain_moments, rg_stain_angle_hist,
     rg_stain_conc_hist) with one small download after each.  batch: feed the set through in pieces of that many tiles, each piece
     adding to the same integers (``accumulate``): the result does not depend on it."""
-    N, H, W = _check(tiles, layout, order, "stain.fit")
+    N, H, W = _tile_args(tiles, layout, order, "stain.fit")
     n_pixels = N * H * W
     if N == 0:
         raise StainFitError("fewer than %d stained pixels" % MIN_STAINED, n_pixels=0, n_stained=0)
     pieces = _pieces(N, H, W, batch)
     cuda = tiles.device.type == "cuda"
     if cuda:
-        lib = _abi.load()
-        dev = tiles.device
         src = tiles.contiguous()
-        D = _Device.get(dev)
-        flags = _flags(layout, order)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        D = _Device.get(tiles.device)
+        flags = export_flags(layout, order)
         mom, ang, con = D.acc[:10], D.acc[10:10 + K + 1], D.acc[10 + K + 1:]
 
-        def run(call):
-            with torch.cuda.device(dev):
-                for i, (a, b) in enumerate(pieces):
-                    call(src[a:b].data_ptr(), b - a, int(i > 0), stream)
+        def run(name, *operands):
+            """the pass `name` over the pieces: operands = what follows (tiles, N, H, W, flags, od_lut) up to the output"""
+            for i, (a, b) in enumerate(pieces):
+                _abi.launch(name, tiles.device, src[a:b].data_ptr(), b - a, H, W, flags, D.od.data_ptr(), *operands, int(i > 0))
     else:
-        rgb = _rgb_numpy(tiles, layout, order)
+        rgb = rgb_numpy(tiles, layout, order)
 
     # pass 1
     if cuda:
-        run(lambda p, n, acc, st: _abi.check(lib.rg_stain_moments(p, n, H, W, flags, D.od.data_ptr(), beta_q(), mom.data_ptr(), acc, st),
-                                             "rg_stain_moments"))
+        run("rg_stain_moments", beta_q(), mom.data_ptr())
         m = mom.cpu().numpy()
     else:
         m = sum(_moments_numpy(rgb[a:b]) for a, b in pieces)
@@ -396,9 +365,7 @@ def fit(tiles, layout="nhwc", order="rgb", batch=None):
     basis6 = quantize_basis(e1, e2)
     # pass 2
     if cuda:
-        b6 = _ii(basis6)
-        run(lambda p, n, acc, st: _abi.check(lib.rg_stain_angle_hist(p, n, H, W, flags, D.od.data_ptr(), beta_q(), _ptr(b6),
-                                                                     D.dirs.data_ptr(), K, ang.data_ptr(), acc, st), "rg_stain_angle_hist"))
+        run("rg_stain_angle_hist", beta_q(), _ii(basis6), D.dirs.data_ptr(), K, ang.data_ptr())
         hist = ang.cpu().numpy()
     else:
         dirs = direction_table()
@@ -408,9 +375,7 @@ def fit(tiles, layout="nhwc", order="rgb", batch=None):
     pinv6 = quantize_pinv(he)
     # pass 3
     if cuda:
-        p6 = _ll(pinv6)
-        run(lambda p, n, acc, st: _abi.check(lib.rg_stain_conc_hist(p, n, H, W, flags, D.od.data_ptr(), _ptr(p6), QP, CSH, CB,
-                                                                    con.data_ptr(), acc, st), "rg_stain_conc_hist"))
+        run("rg_stain_conc_hist", _ll(pinv6), QP, CSH, CB, con.data_ptr())
         chist = con.cpu().numpy().reshape(2, CB)
     else:
         chist = sum(_conc_hist_numpy(rgb[a:b], pinv6) for a, b in pieces)
@@ -422,7 +387,7 @@ def normalize(tiles, fit, target=REFERENCE_TARGET, out=None, layout="nhwc", orde
     """Re-render `tiles` (fitted by `fit`) with the stain vectors and concentrations of `target` (a StainFit) -> uint8 tensor of the
     same shape, layout, channel order and device.  out: None (a new tensor), or a contiguous uint8 tensor of tiles' shape on its
     device; ``out=tiles`` normalises in place (tiles must then be contiguous).  One launch (rg_stain_apply) on a CUDA tensor."""
-    N, H, W = _check(tiles, layout, order, "stain.normalize")
+    N, H, W = _tile_args(tiles, layout, order, "stain.normalize")
     if not isinstance(fit, StainFit) or not isinstance(target, StainFit):
         raise ValueError("fit and target are StainFit objects")
     pinv6, scale2, href6 = apply_operands(fit, target)
@@ -437,20 +402,15 @@ def normalize(tiles, fit, target=REFERENCE_TARGET, out=None, layout="nhwc", orde
     if N == 0:
         return out
     if tiles.device.type != "cuda":
-        res = _apply_numpy(np.ascontiguousarray(_rgb_numpy(tiles, layout, order)), pinv6, scale2, href6)
-        _rgb_numpy(out, layout, order)[...] = res
+        res = _apply_numpy(np.ascontiguousarray(rgb_numpy(tiles, layout, order)), pinv6, scale2, href6)
+        rgb_numpy(out, layout, order)[...] = res
         return out
-    lib = _abi.load()
-    dev = tiles.device
     src = tiles if inplace else tiles.contiguous()
-    D = _Device.get(dev)
+    D = _Device.get(tiles.device)
     p6, s2, h6 = _ll(pinv6), _ll(scale2), _ii(href6)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        for a, b in _pieces(N, H, W, None):
-            _abi.check(lib.rg_stain_apply(src[a:b].data_ptr(), out[a:b].data_ptr(), b - a, H, W, _flags(layout, order), D.od.data_ptr(),
-                                          _ptr(p6), QP, _ptr(s2), QS, _ptr(h6), QH + QOD - QO, D.out.data_ptr(), D.L, D.off, stream),
-                       "rg_stain_apply")
+    for a, b in _pieces(N, H, W, None):
+        _abi.launch("rg_stain_apply", tiles.device, src[a:b].data_ptr(), out[a:b].data_ptr(), b - a, H, W, export_flags(layout, order),
+                    D.od.data_ptr(), p6, QP, s2, QS, h6, QH + QOD - QO, D.out.data_ptr(), D.L, D.off)
     return out
 
 

@@ -171,7 +171,7 @@ def _box_numpy(a, f):
 
 # ------------------------------------------------------------------ the public functions
 def _device_table(n_in, n_out, dev):
-    key = (n_in, n_out, dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (n_in, n_out) + _abi.device_key(dev)
     t = _TABLES.get(key)
     if t is None:
         bounds, coef = _tables(n_in, n_out)
@@ -215,13 +215,10 @@ def resize_windows(raster, origins, read_size, out_size, order="rgb"):
     src = raster.contiguous()
     xt = None if w == ow else _device_table(w, ow, dev)
     yt = None if h == oh else _device_table(h, oh, dev)
-    lib = _abi.load()
-    with torch.cuda.device(dev):
-        _abi.check(lib.rg_window_resize_u8(src.data_ptr(), src.shape[0], src.shape[1], o.data_ptr(), N, h, w, oh, ow,
-                                           None if xt is None else xt.data_ptr(), 0 if xt is None else xt.shape[1] - 2,
-                                           None if yt is None else yt.data_ptr(), 0 if yt is None else yt.shape[1] - 2,
-                                           out.data_ptr(), RG_EXPORT_REVERSE if order == "bgr" else 0,
-                                           torch.cuda.current_stream(dev).cuda_stream), "rg_window_resize_u8")
+    _abi.launch("rg_window_resize_u8", dev, src.data_ptr(), src.shape[0], src.shape[1], o.data_ptr(), N, h, w, oh, ow,
+                None if xt is None else xt.data_ptr(), 0 if xt is None else xt.shape[1] - 2,
+                None if yt is None else yt.data_ptr(), 0 if yt is None else yt.shape[1] - 2,
+                out.data_ptr(), RG_EXPORT_REVERSE if order == "bgr" else 0)
     return out
 
 
@@ -244,9 +241,7 @@ def erode(mask, radius):
         src = m.contiguous()
         out = torch.empty_like(src)
         if N:
-            with torch.cuda.device(m.device):
-                _abi.check(_abi.load().rg_mask_erode(src.data_ptr(), out.data_ptr(), N, H, W, radius,
-                                                     torch.cuda.current_stream(m.device).cuda_stream), "rg_mask_erode")
+            _abi.launch("rg_mask_erode", m.device, src.data_ptr(), out.data_ptr(), N, H, W, radius)
     return out if mask.dim() == 3 else out[0]
 
 
@@ -263,9 +258,7 @@ def thumbnail(raster, factor):
     src = raster.contiguous()
     RH, RW = src.shape[:2]
     out = torch.empty((-(-RH // factor), -(-RW // factor), 3), dtype=torch.uint8, device=src.device)
-    with torch.cuda.device(src.device):
-        _abi.check(_abi.load().rg_box_reduce_u8(src.data_ptr(), RH, RW, factor, out.data_ptr(),
-                                                torch.cuda.current_stream(src.device).cuda_stream), "rg_box_reduce_u8")
+    _abi.launch("rg_box_reduce_u8", src.device, src.data_ptr(), RH, RW, factor, out.data_ptr())
     return out
 
 

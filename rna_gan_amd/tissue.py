@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .export import LAYOUTS, ORDERS, RG_EXPORT_PLANAR, RG_EXPORT_REVERSE
+from .export import RG_EXPORT_PLANAR, RG_EXPORT_REVERSE, export_flags, rgb_numpy, tile_args  # noqa: F401 (the flag bits: tests/test_tissue_refs_cpu.py reads them here)
 
 MAX_DILATE = 8
 MAX_PIXELS = 1 << 26
@@ -75,16 +75,7 @@ def percentile_ranks(n, percentiles=(1, 99)):
 
 
 def _check(tiles, layout, order, rgb_min, dilate):
-    if layout not in LAYOUTS:
-        raise ValueError("layout must be one of %s" % (LAYOUTS,))
-    if order not in ORDERS:
-        raise ValueError("order must be one of %s" % (ORDERS,))
-    if not torch.is_tensor(tiles) or tiles.dim() != 4 or tiles.dtype != torch.uint8:
-        raise ValueError("tile_stats takes a uint8 (N, H, W, 3) or (N, 3, H, W) tensor")
-    if tiles.shape[3 if layout == "nhwc" else 1] != 3:
-        raise ValueError("tile_stats needs 3 channels in layout %s, got %s" % (layout, tuple(tiles.shape)))
-    N = tiles.shape[0]
-    H, W = (tiles.shape[1], tiles.shape[2]) if layout == "nhwc" else (tiles.shape[2], tiles.shape[3])
+    N, H, W = tile_args(tiles, layout, order, "tile_stats")
     if H < 1 or W < 1 or H * W > MAX_PIXELS:
         raise ValueError("tile_stats needs 1 <= H W <= 2^26, got H %d W %d" % (H, W))
     if not 0 <= int(rgb_min) <= 255:
@@ -158,12 +149,7 @@ def tile_stats(tiles, layout="nhwc", order="rgb", rgb_min=50, dilate=3, percenti
         mask = torch.empty((0, H, W), dtype=torch.uint8, device=tiles.device) if return_mask else None
         return TileStats(np.zeros((0, 12), np.int32), H, W, ranks, weights, percentiles, rgb_min, dilate, mask)
     if tiles.device.type != "cuda":
-        a = tiles.numpy()
-        if layout == "nchw":
-            a = a.transpose(0, 2, 3, 1)
-        if order == "bgr":
-            a = a[..., ::-1]
-        stats, mask = _tile_stats_numpy(a, rgb_min, dilate, ranks, return_mask)
+        stats, mask = _tile_stats_numpy(rgb_numpy(tiles, layout, order), rgb_min, dilate, ranks, return_mask)
         return TileStats(stats, H, W, ranks, weights, percentiles, rgb_min, dilate, None if mask is None else torch.from_numpy(mask))
     stats, mask = tile_stats_device(tiles, layout, order, rgb_min, dilate, percentiles, return_mask)
     return TileStats(stats.cpu().numpy(), H, W, ranks, weights, percentiles, rgb_min, dilate, mask)
@@ -186,18 +172,13 @@ def tile_stats_device(tiles, layout="nhwc", order="rgb", rgb_min=50, dilate=3, p
     if N == 0:
         return out, mask
     src = tiles.contiguous()
-    lib = _abi.load()
-    flags = (RG_EXPORT_PLANAR if layout == "nchw" else 0) | (RG_EXPORT_REVERSE if order == "bgr" else 0)
-    need = int(lib.rg_tile_qc_workspace_bytes(N, H, W))
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    need = int(_abi.load().rg_tile_qc_workspace_bytes(N, H, W))
+    key = _abi.device_key(dev)
     ws = _WS.get(key)                       # one buffer per device: calls on one stream follow each other and each zeroes it first
     if ws is None or ws.numel() < need:
         ws = _WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    r4 = (ctypes.c_int * 4)(*ranks)
-    with torch.cuda.device(dev):
-        _abi.check(lib.rg_tile_qc(src.data_ptr(), N, H, W, flags, int(rgb_min), int(dilate), ctypes.cast(r4, ctypes.c_void_p),
-                                  out.data_ptr(), None if mask is None else mask.data_ptr(), ws.data_ptr(), ws.numel(),
-                                  torch.cuda.current_stream(dev).cuda_stream), "rg_tile_qc")
+    _abi.launch("rg_tile_qc", dev, src.data_ptr(), N, H, W, export_flags(layout, order), int(rgb_min), int(dilate),
+                (ctypes.c_int * 4)(*ranks), out.data_ptr(), None if mask is None else mask.data_ptr(), ws.data_ptr(), ws.numel())
     return out, mask
 
 

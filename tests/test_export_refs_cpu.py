@@ -107,6 +107,57 @@ def test_tiles_u8_refusals():
     assert (EX.RG_EXPORT_PLANAR, EX.RG_EXPORT_REVERSE, EX.RG_EXPORT_TRUNC) == (X.PLANAR, X.REVERSE, X.TRUNC) == (1, 2, 4)
 
 
+# ------------------------------------------------------------------------------------- the argument layer of the uint8 image side
+def test_tile_args_refuses_what_stain_and_tissue_refused():
+    from rna_gan_amd import stain, tissue
+    ok = torch.zeros((2, 5, 7, 3), dtype=torch.uint8)
+    assert EX.tile_args(ok, "nhwc", "bgr", "f") == (2, 5, 7) and EX.tile_args(ok.permute(0, 3, 1, 2), "nchw", "rgb", "f") == (2, 5, 7)
+    takes = "%s takes a uint8 (N, H, W, 3) or (N, 3, H, W) tensor"
+    cases = [((ok.float(), "nhwc", "rgb"), takes),                                                           # a wrong dtype
+             ((ok[0], "nhwc", "rgb"), takes),                                                                # a wrong rank
+             ((ok.numpy(), "nhwc", "rgb"), takes),
+             ((ok, "nchw", "rgb"), "%s needs 3 channels in layout nchw, got (2, 5, 7, 3)"),                 # a wrong channel count
+             ((ok[..., :2], "nhwc", "rgb"), "%s needs 3 channels in layout nhwc, got (2, 5, 7, 2)"),
+             ((ok, "hwc", "rgb"), "layout must be one of ('nhwc', 'nchw')"),
+             ((ok, "nhwc", "grb"), "order must be one of ('rgb', 'bgr')"),
+             ((ok.float(), "hwc", "grb"), "layout must be one of ('nhwc', 'nchw')")]                        # the order of the checks
+    for (tiles, layout, order), text in cases:
+        for what, call in (("f", lambda: EX.tile_args(tiles, layout, order, "f")),
+                           ("stain.fit", lambda: stain.fit(tiles, layout, order)),
+                           ("stain.normalize", lambda: stain.normalize(tiles, stain.REFERENCE_TARGET, layout=layout, order=order)),
+                           ("tile_stats", lambda: tissue.tile_stats(tiles, layout, order))):
+            with pytest.raises(ValueError) as e:
+                call()
+            assert type(e.value) is ValueError and str(e.value) == (text % what if "%s" in text else text), (what, text)
+    empty = torch.zeros((2, 0, 7, 3), dtype=torch.uint8)                       # each module keeps its own rule for H W = 0
+    assert EX.tile_args(empty, "nhwc", "rgb", "f") == (2, 0, 7)
+    with pytest.raises(ValueError, match="stain.fit needs H, W >= 1"):
+        stain.fit(empty)
+    with pytest.raises(ValueError, match="tile_stats needs 1 <= H W <= 2\\^26, got H 0 W 7"):
+        tissue.tile_stats(empty)
+
+
+def test_rgb_numpy_equals_the_four_views():
+    rgb = np.random.default_rng(8).integers(0, 256, (2, 3, 5, 3), dtype=np.uint8)
+    stored = {("nhwc", "rgb"): rgb, ("nhwc", "bgr"): rgb[..., ::-1], ("nchw", "rgb"): rgb.transpose(0, 3, 1, 2),
+              ("nchw", "bgr"): rgb[..., ::-1].transpose(0, 3, 1, 2)}
+    for (layout, order), a in stored.items():
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        got = EX.rgb_numpy(t, layout, order)
+        assert got.shape == (2, 3, 5, 3) and np.array_equal(got, rgb), (layout, order)
+        assert np.shares_memory(got, t.numpy()), "a view, not a copy"
+
+
+def test_a_ctypes_array_reaches_a_void_pointer_parameter():
+    """what _abi.launch relies on for small host operands: no cast in front of a c_void_p parameter"""
+    memcpy = ctypes.CDLL(None).memcpy
+    memcpy.restype, memcpy.argtypes = ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    for ctype, values in ((ctypes.c_int, [3, -30000, 2 ** 31 - 1, -2 ** 31]), (ctypes.c_longlong, [1 << 40, -(1 << 40) - 1, 0, 7])):
+        src, dst = (ctype * 4)(*values), (ctype * 4)()
+        memcpy(dst, src, ctypes.sizeof(src))
+        assert list(dst) == values
+
+
 # ---------------------------------------------------------------------------------------------------------------- stored frames
 def _sizes():
     header = len(pickle.dumps(("slide_patch_0", b"", (256, 256, 3))))

@@ -83,16 +83,16 @@ def kernel_section(device, N, S, reps, rounds):
         _abi.check(lib.rg_stain_moments(src(), N, S, S, 0, D.od.data_ptr(), stain.beta_q(), D.acc.data_ptr(), 0, st), "moments")
 
     def angle():
-        _abi.check(lib.rg_stain_angle_hist(src(), N, S, S, 0, D.od.data_ptr(), stain.beta_q(), stain._ptr(basis6), D.dirs.data_ptr(),
+        _abi.check(lib.rg_stain_angle_hist(src(), N, S, S, 0, D.od.data_ptr(), stain.beta_q(), basis6, D.dirs.data_ptr(),
                                            stain.K, D.acc[10:].data_ptr(), 0, st), "angle")
 
     def conc():
-        _abi.check(lib.rg_stain_conc_hist(src(), N, S, S, 0, D.od.data_ptr(), stain._ptr(p6), stain.QP, stain.CSH, stain.CB,
+        _abi.check(lib.rg_stain_conc_hist(src(), N, S, S, 0, D.od.data_ptr(), p6, stain.QP, stain.CSH, stain.CB,
                                           D.acc[10 + stain.K + 1:].data_ptr(), 0, st), "conc")
 
     def apply():
-        _abi.check(lib.rg_stain_apply(src(), out.data_ptr(), N, S, S, 0, D.od.data_ptr(), stain._ptr(p6), stain.QP, stain._ptr(s2),
-                                      stain.QS, stain._ptr(h6), stain.QH + stain.QOD - stain.QO, D.out.data_ptr(), D.L, D.off, st), "apply")
+        _abi.check(lib.rg_stain_apply(src(), out.data_ptr(), N, S, S, 0, D.od.data_ptr(), p6, stain.QP, s2,
+                                      stain.QS, h6, stain.QH + stain.QOD - stain.QO, D.out.data_ptr(), D.L, D.off, st), "apply")
 
     def copy():
         out.copy_(data[(k[0] + 1) % sets])
