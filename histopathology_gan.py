@@ -105,6 +105,12 @@ EXTRA_FLAGS = [
                              "generated tiles that the reference tiler's acceptance rule keeps -- a tissue mask over more than "
                              "20 % of the tile, not low-contrast (rna_gan_amd.tissue, on the device; no real tiles are judged); "
                              "with another metric over N samples it shares the noise (0 = off)"),
+    ("--div_samples", int, 0, "evaluate the pixel-space diversity (rna_gan_amd.metrics.PairDiversity) after every epoch: the mean "
+                              "MS-SSIM over random pairs of N generated tiles, next to the same pairs of the first N items of the "
+                              "dataset (turned back to bytes); generated pairs clearly more similar than real ones, or a sudden "
+                              "rise between epochs, mean mode collapse; no feature extractor is involved; with another metric "
+                              "over N samples it shares the noise (0 = off, otherwise at least 2)"),
+    ("--div_pairs", int, 0, "--div_samples: how many random pairs (0 = as many as samples)"),
     ("--cf_patients", int, 0, "--loss_type wganvae only: evaluate the conditioning fidelity "
                               "(rna_gan_amd.metrics.ConditioningFidelity) after every epoch over the first P distinct RNA rows of "
                               "the dataset: per patient, the mean features (--fd_extractor) of its real tiles and of --cf_tiles "
@@ -186,6 +192,10 @@ def parse_args(argv=None):
         ap.error("--pr_samples must be 0 (off) or at least --pr_k + 1 (a k-th neighbour needs k other samples)")
     if args.qc_samples < 0 or args.qc_samples == 1:
         ap.error("--qc_samples must be 0 (off) or at least 2")
+    if args.div_samples < 0 or args.div_samples == 1:
+        ap.error("--div_samples must be 0 (off) or at least 2 (a pair needs two tiles)")
+    if args.div_pairs < 0:
+        ap.error("--div_pairs must be >= 0")
     if args.pr_report not in ("precision", "recall", "density", "coverage"):
         ap.error("--pr_report must be precision, recall, density or coverage")
     if args.cf_patients < 0 or args.cf_patients == 1:
@@ -289,6 +299,17 @@ def build_qc_metric(args, ds, losses, device, holder):
     from rna_gan_amd.metrics import TissueYield
     real, _extractor, noise, batch = metric_inputs(args, args.qc_samples, "--qc_samples", ds, losses, device, holder)
     return TissueYield(int(real.shape[0]), noise=noise, seed=args.seed, batch_size=batch)
+
+
+def build_div_metric(args, ds, losses, device, holder):
+    """--div_samples: the mean MS-SSIM over random pairs of N generated tiles.  metric_inputs supplies the noise (shared with the
+    other metrics over N samples) and the first N readable items, which -- turned back to the bytes they were decoded from by
+    ``export.tiles_u8`` -- are the real baseline the same pair list is evaluated over."""
+    from rna_gan_amd.export import tiles_u8
+    from rna_gan_amd.metrics import PairDiversity
+    real, _extractor, noise, batch = metric_inputs(args, args.div_samples, "--div_samples", ds, losses, device, holder)
+    return PairDiversity(int(real.shape[0]), pairs=args.div_pairs or None, real=tiles_u8(real.float().contiguous()), noise=noise,
+                         seed=args.seed, batch_size=batch)
 
 
 def build_mem_metric(args, ds, losses, device, holder):
@@ -463,6 +484,8 @@ def main():
             metrics.append(build_pr_metric(args, ds, losses, device, holder))
         if args.qc_samples > 0:
             metrics.append(build_qc_metric(args, ds, losses, device, holder))
+        if args.div_samples > 0:
+            metrics.append(build_div_metric(args, ds, losses, device, holder))
         if args.cf_patients > 0:
             metrics.append(build_cf_metric(args, ds, losses, device, holder))
         if args.mem_samples > 0:

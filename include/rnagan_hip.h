@@ -1155,6 +1155,54 @@ size_t rg_nn_topk_ws_bytes(int Q, long long N, int k);
 int rg_nn_topk_i8(const int8_t* a, const int32_t* na2, int Q, const int8_t* b, const int32_t* nb2, long long N, int D, long long ldd,
                   int k, const int32_t* exclude, uint64_t* keys, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- MS-SSIM between pairs of uint8 RGB tiles (rna_gan_amd/csrc/rg_msssim.hip) ----
+ * rna_gan_amd.msssim asks how similar pairs of tiles are in pixel space (Wang, Simoncelli & Bovik 2003); the mean over random
+ * pairs of generated tiles is the diversity score of rna_gan_amd.metrics.PairDiversity.  tests/msssim_refs.py restates this in numpy.
+ *
+ * Definition, per channel of two tiles x, y of H x W:
+ *   window   11 taps g (the host's fp64 Gaussian, sigma 1.5, normalised to sum 1), applied separably with valid extent: a level
+ *            of h x w has (h - 10) (w - 10) window positions.
+ *   pyramid  level 0 is the bytes; a pixel of level s is the exact integer sum of the aligned 2^s x 2^s block of bytes, divided
+ *            by 4^s; h_s = H >> s, w_s = W >> s (a last odd row or column is dropped level by level).
+ *   level    with the window means mx, my, E[x^2], E[y^2], E[xy]:  vx = E[x^2] - mx^2, vy likewise, cxy = E[xy] - mx my,
+ *              cs = (2 cxy + C2) / (vx + vy + C2),   l = (2 mx my + C1) / (mx^2 + my^2 + C1),   C1 = 2.55^2, C2 = 7.65^2.
+ *   result   out[P][S][3][2] fp64: per pair, level and channel (R, G, B) the SUMS of cs and of l cs over the window positions.
+ *            The host divides by the position count, clamps, raises to the level weights and multiplies.
+ *
+ * rg_msssim_plan      S levels, 1 <= S <= 5, need min(H, W) >> (S - 1) >= 11.  info (NULL, or int32 [2 + 2 S]) receives
+ *                     RG_MSSSIM_BAND, RG_MSSSIM_COLS, then (h_s, w_s) for s = 0 .. S - 1.  *pyramid_tile_bytes: what
+ *                     rg_msssim_pyramid writes per tile (0 for S == 1); *pair_ws_bytes: the workspace of rg_msssim_pairs for P pairs.
+ *                     Either may be NULL.  RG_EINVAL for H or W < 11, a bad S, P < 0; RG_EUNSUPPORTED for H or W > 4096 or more than
+ *                     2^31 - 1 workgroups.
+ * rg_msssim_pyramid   tiles: N tiles of H x W pixels, 3 channels, uint8, any alignment.  flags: RG_EXPORT_PLANAR clear:
+ *                     [N][H][W][3], set: [N][3][H][W]; RG_EXPORT_REVERSE: the stored channel order is B, G, R.  No other bit.
+ *                     pyr receives, per tile (pyramid_tile_bytes apart), levels 1 .. S - 1 one after the other, each uint16
+ *                     [3][h_s][w_s] in R, G, B order: the block sums (at most 255 * 256).  2-byte aligned.  Built once per tile: the
+ *                     pairs reuse it.  One launch; S == 1 or N == 0: RG_OK, nothing launched (pyr may be NULL for S == 1).
+ * rg_msssim_pairs     pair p compares tile ia[p] of set a with tile ib[p] of set b (int32 on the device, [0, Na) and [0, Nb); the
+ *                     host cannot see them: an index outside its set makes the six doubles per level of that pair NaN and is
+ *                     never used as an address).  a and b may be the same set; both have the shape H x W and the layout `flags`.
+ *                     pyr_a, pyr_b: their pyramids (NULL for S == 1).  taps: ELEVEN HOST doubles.
+ *                     A workgroup owns RG_MSSSIM_BAND x RG_MSSSIM_COLS window positions of one level and channel of one pair: it
+ *                     stages the (BAND + 10) x (COLS + 10) pixels of both tiles once in LDS, takes the five horizontal moments of
+ *                     every staged row into LDS, the vertical pass and the two ratios out of it, and reduces in a fixed order to
+ *                     one partial pair in ws; a second launch adds the partials of a (pair, level, channel) in ascending
+ *                     workgroup order and WRITES out.  fp64 throughout, no atomics: the doubles of a pair depend on the two tiles'
+ *                     bytes alone -- not on P, on the pair's position, on the other pairs or on which set a tile is read from.
+ *                     ws: pair_ws_bytes, 8-byte aligned, contents irrelevant before and after.  Two launches on `stream`; no host
+ *                     synchronisation, no allocation, safe under graph capture.  P == 0: RG_OK once shape, S and flags are
+ *                     accepted; no pointer is looked at, nothing launched, nothing written.
+ * Nothing is launched or written on an error: RG_EINVAL for a NULL tiles / index / taps / out buffer, a NULL pyramid with S > 1,
+ * N, Na or Nb < 1 with work to do, P < 0, H or W < 11, a bad S, an unknown flag bit, a misaligned pyramid, index array, ws or out;
+ * RG_EWORKSPACE for pyr_bytes below N pyramid_tile_bytes and for a NULL or short ws.  No 16-bit FLOAT type is involved: both builds behave identically. */
+#define RG_MSSSIM_BAND 32
+#define RG_MSSSIM_COLS 16
+int rg_msssim_plan(int H, int W, int S, int P, int32_t* info, size_t* pyramid_tile_bytes, size_t* pair_ws_bytes);
+int rg_msssim_pyramid(const uint8_t* tiles, int N, int H, int W, int flags, int S, void* pyr, size_t pyr_bytes, void* stream);
+int rg_msssim_pairs(const uint8_t* a, const void* pyr_a, int Na, const uint8_t* b, const void* pyr_b, int Nb, const int32_t* ia,
+                    const int32_t* ib, int P, int H, int W, int flags, int S, const double* taps, void* ws, size_t ws_bytes,
+                    double* out, void* stream);
+
 /* ---- the fp32 mode on the bf16 matrix cores, operands split ONCE PER TENSOR (rna_gan_amd/csrc/rg_conv8f.hip, rg_wgrad8f.hip) ----
  * The reference computes in fp32 (src/betaVAE.py:184,223; the GAN CLI never enables AMP).  An fp32 value is the exact sum of three
  * bf16 numbers v = h + m + l; rg_split_planes writes them as a plane-major buffer planes[3][n] (bf16, n % 8 == 0) in one

@@ -160,6 +160,9 @@ PROTOTYPES = {
     "rg_tile_descriptor_i8": (_i, [_p, _i, _i, _i, _i, _p, C.c_longlong, _p, _p]),
     "rg_nn_topk_ws_bytes": (_z, [_i, C.c_longlong, _i]),
     "rg_nn_topk_i8": (_i, [_p, _p, _i, _p, _p, C.c_longlong, _i, C.c_longlong, _i, _p, _p, _p, _z, _p]),
+    "rg_msssim_plan": (_i, [_i, _i, _i, _i, _p, _p, _p]),
+    "rg_msssim_pyramid": (_i, [_p, _i, _i, _i, _i, _i, _p, _z, _p]),
+    "rg_msssim_pairs": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _z, _p, _p]),
     "rg_conv_up_fp8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _f, _i, _p]),
     "rg_gemm_fp8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _f, _i, _p]),
     "rg_fp8_supported": (_i, [_i, _i, _i, _i]),
@@ -222,7 +225,7 @@ PROTOTYPES = {
 }
 
 # must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES when an existing entry
-# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three, rg_tile_gather_transform, rg_rows_gather_f32, rg_groupstat.hip's two, rg_stain.hip's four, rg_nn.hip's three, rg_linprobe.hip's four) keeps the number -- load() refuses a library that lacks it
+# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three, rg_tile_gather_transform, rg_rows_gather_f32, rg_groupstat.hip's two, rg_stain.hip's four, rg_nn.hip's three, rg_linprobe.hip's four, rg_msssim.hip's three) keeps the number -- load() refuses a library that lacks it
 ABI_VERSION = 618
 
 _libs = {}

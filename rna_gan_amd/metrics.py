@@ -20,6 +20,9 @@ background".
 ``Memorisation`` asks the question all of the above answer the wrong way round -- a generator that copies its training tiles
 scores BETTER on each of them: the exact nearest training tiles of the generated tiles (rna_gan_amd.nearest: rg_tile_descriptor_i8,
 rg_nn_topk_i8) and the fraction that is closer to one than any other training tile is.
+``PairDiversity`` asks whether the generated tiles differ from EACH OTHER, in pixel space and without an extractor: the mean MS-SSIM
+over fixed random pairs of generated tiles (rna_gan_amd.msssim: rg_msssim_pyramid, rg_msssim_pairs), next to the same figure over
+real tiles -- the early sign of mode collapse.
 """
 from __future__ import annotations
 
@@ -582,3 +585,81 @@ class Memorisation(_GeneratedSamples):
         self.last = self.calculate_score(torch.cat(self.generated_tiles(generator, device)))
         self.history.append(dict(self.last))
         return float(self.last["copy_rate"])
+
+
+class PairDiversity(_GeneratedSamples):
+    """Are the generated tiles different from each other?  The mean MS-SSIM over ``pairs`` fixed random pairs of ``samples`` generated
+    tiles (Odena et al. 2017; rna_gan_amd.msssim: rg_msssim_pyramid, rg_msssim_pairs) -- the pixel-space sign of mode collapse that
+    needs no feature extractor: a collapsing generator keeps its tissue yield, copies nothing and moves the critic-feature distances
+    only slowly, while its tiles grow alike.  ``samples`` generated images go through ``synthesize`` -> ``export.tiles_u8`` (the bytes
+    a tile store would hold) -> the pair launch; P * S * 6 doubles reach the host.
+
+    pairs     how many pairs (default: ``samples``); the list is ``msssim.random_pairs(samples, pairs, seed)``, the same at every
+              evaluation, and never pairs a tile with itself.
+    real      None, or real uint8 tiles -- (N, 3, H, W) or (N, H, W, 3), or a resident.DeviceTileSet -- of the generated tiles' size,
+              N >= samples: the SAME pair list is evaluated over them once, at the first evaluation, and cached.  Generated pairs
+              clearly more similar than real pairs (a positive ``gap``) mean collapse.
+    scales    S of ``msssim.components`` (default: the largest the tile size allows).
+    noise, seed, batch_size, encoding_dims: as TissueYield; the generator runs in eval mode under no_grad, its mode is restored.
+    ``metric_ops`` returns the mean MS-SSIM of the generated pairs (what the trainer logs); ``self.last`` and, per evaluation,
+    ``self.history`` keep {"generated", "real", "gap" (generated - real; both None without real tiles), "per_scale" ([S][2]: the means
+    of CS_s and SSIM_s over the generated pairs)}; the per-pair scores of the last evaluation are ``self.last_scores``.
+    Pickling keeps the settings and ``history``, never the noise or the tiles (``set_real`` re-supplies the real tiles)."""
+
+    def __init__(self, samples, pairs=None, real=None, scales=None, noise=None, seed=0, batch_size=256, encoding_dims=None):
+        super().__init__(samples, noise, seed, batch_size, encoding_dims, count="samples", least=2)
+        self.pairs = self.n_fake if pairs is None else int(pairs)
+        if self.pairs < 1:
+            raise ValueError("pairs must be >= 1")
+        self.scales = None if scales is None else int(scales)
+        if self.scales is not None and not 1 <= self.scales <= 5:
+            raise ValueError("scales must be in 1..5")
+        self.last, self.last_scores, self.history = None, None, []
+        self.real = self._real_score = None
+        self.set_real(real)
+
+    def set_real(self, real):
+        tiles = getattr(real, "tiles", real)
+        if tiles is not None:
+            if not torch.is_tensor(tiles) or tiles.dtype != torch.uint8 or tiles.dim() != 4 or 3 not in (tiles.shape[1], tiles.shape[3]):
+                raise ValueError("real must be uint8 tiles, (N, 3, H, W) or (N, H, W, 3), or a DeviceTileSet")
+            if tiles.shape[0] < self.n_fake:
+                raise ValueError("real holds %d tiles, the pair list runs over %d" % (tiles.shape[0], self.n_fake))
+        self.real, self._real_score = tiles, None
+
+    def __getstate__(self):
+        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
+                "pairs": self.pairs, "scales": self.scales, "history": [dict(h) for h in self.history]}
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.real = self._real_score = None
+        self.last, self.last_scores = None, None
+        self.history = [dict(h) for h in state.get("history", [])]
+
+    def pair_list(self):
+        from .msssim import random_pairs
+        return random_pairs(self.n_fake, self.pairs, self.seed)
+
+    def preprocess(self, x):
+        """fp32 [-1, 1] NCHW images -> the uint8 tiles a store would hold (interleaved RGB, the rounding rule), on the device."""
+        from .export import tiles_u8
+        return tiles_u8(x.float().contiguous())
+
+    def calculate_score(self, tiles, layout="nhwc"):
+        """(the per-pair MS-SSIM, the diversity dictionary) of the metric's pair list over a tile set"""
+        from . import msssim as MS
+        comp = MS.components(tiles, None, self.pair_list(), self.scales, layout)
+        return MS.finish(comp), MS.diversity_of(comp)
+
+    def metric_ops(self, generator, device):
+        tiles = torch.cat(self.generated_tiles(generator, device))
+        self.last_scores, gen = self.calculate_score(tiles)
+        if self.real is not None and self._real_score is None:
+            real = self.real.to(device)
+            self._real_score = self.calculate_score(real, "nchw" if real.shape[1] == 3 else "nhwc")[1]["mean"]
+        real = self._real_score
+        self.last = {"generated": gen["mean"], "real": real, "gap": None if real is None else gen["mean"] - real,
+                     "per_scale": gen["per_scale"]}
+        self.history.append(dict(self.last))
+        return float(gen["mean"])
