@@ -232,8 +232,8 @@ def metric_inputs(args, n_samples, flag, ds, losses, device, holder):
     the metric's own rows (no collective).  ``holder["trainer"]`` is filled in once the Trainer exists: the noise needs its
     generator.  ``holder`` also keeps what is built here, so two metrics over the same number of samples share one device copy of
     the real set and one noise callable, and all metrics share one extractor."""
-    from rna_gan_amd import _abi
     from rna_gan_amd.fid import inception_features_device
+    from rna_gan_amd.representation import latent_prep
     if "extractor" not in holder:
         holder["extractor"] = "discriminator" if args.fd_extractor == "discriminator" else \
             inception_features_device(args.fd_extractor, device)
@@ -267,10 +267,7 @@ def metric_inputs(args, n_samples, flag, ds, losses, device, holder):
                 with torch.no_grad():
                     z = betavae.encode(rna.to(device))[0].detach().float().contiguous()
                 betavae.train(was_training)
-                out = torch.empty_like(u)
-                _abi.check(_abi.load().rg_latent_prep(u.data_ptr(), z.data_ptr(), out.data_ptr(), n, E,
-                                                      torch.cuda.current_stream(device).cuda_stream), "rg_latent_prep")
-                cache["z"] = out
+                cache["z"] = latent_prep(u, z)
             return cache["z"]
     shared[n_samples] = (real, holder["extractor"], noise, min(256, len(items)))
     return shared[n_samples]

@@ -1,4 +1,8 @@
-"""ctypes binding of librnagan_hip.so (include/rnagan_hip.h).
+"""ctypes binding of librnagan_hip.so.  include/rnagan_hip.h is the only statement of the ABI: PROTOTYPES and CONSTANTS are
+read from it at import, so a new entry point is a declaration in the header and a definition in a .hip file, nothing else.
+
+Everything outside the training-step backend calls a stream-taking entry point through launch(); entry points without a
+stream (*_ws_bytes, *_workspace_bytes, rg_msssim_plan) are called as load().name(...).
 
 There is NO fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
@@ -6,226 +10,61 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librnagan_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rnagan_hip.h")
 
-RG_F32, RG_BF16, RG_F16 = 0, 1, 2
-RG_U8 = 3            # a source type only (rg_resize_bilinear01, rg_tile_transform)
-ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA = 0, 1, 2
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "int64_t": C.c_int64,
+            "long long": C.c_longlong, "unsigned": C.c_uint}
+# the short names the family tests (tests/test_*_refs_cpu.py) spell their pinned prototypes with; nothing in the package uses them
+_p, _i, _f, _d, _z, _l = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_int64
+_TYPE_WORDS = frozenset("void char short int long unsigned signed float double size_t int64_t const".split())
 
-_p = C.c_void_p
-_i = C.c_int
-_f = C.c_float
-_d = C.c_double
-_z = C.c_size_t
-_l = C.c_int64
 
-# name -> (restype, [argtypes])   -- must list every symbol declared in include/rnagan_hip.h
-PROTOTYPES = {
-    "rg_version": (_i, []),
-    "rg_last_error": (C.c_char_p, []),
-    "rg_set_option": (_i, [C.c_char_p, _i]),
-    "rg_pack_conv_weight": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "rg_conv_stats_rows": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_down": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _z, _p]),
-    "rg_conv_up": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p, _i, _i, _p, _z, _p]),
-    "rg_conv_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_wgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_conv_wgrad2": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_conv_wgrad_slabs": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p, _p, _p]),
-    "rg_grad_to_wire": (_i, [_p, _p, _z, _i, _p, _p, _p, _p, _p, _p]),
-    "rg_conv_wgrad_wire": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_conv_wgrad_adam_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_wgrad_adam": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_first_down": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "rg_first_down_bits": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "rg_sign_pack": (_i, [_p, _p, C.c_longlong, _i, _i, _p]),
-    "rg_first_down_masked_supported": (_i, [_i, _i, _i, _i, _i]),
-    "rg_first_down_masked": (_i, [_p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_conv_up_maskbits_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_up_maskbits": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p, _z, _p]),
-    "rg_last_up": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_skinny_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "rg_skinny_wgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_skinny_wgrad_slabs": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _z, _p, _p, _p, _p]),
-    "rg_skinny_wgrad_bias": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p, _p]),
-    "rg_pack_g0_weight": (_i, [_p, _p, _i, _i, _i, _p]),
-    "rg_pack_conv_wup_from_bf16": (_i, [_p, _p, _i, _i, _p]),
-    "rg_pack_conv_wup_from_bf16_multi": (_i, [_i, _p, _p, _p, _p, _p]),
-    "rg_pack_g0_weight_from_bf16": (_i, [_p, _p, _i, _i, _p]),
-    "rg_g0_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_g0_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "rg_g0_wgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_head_fwd": (_i, [_p, _p, _p, _p, _i, _i, _f, _i, _p]),
-    "rg_head_grad": (_i, [_p, _p, _i, _f, _f, _p]),
-    "rg_head_grad_dev": (_i, [_p, _p, _i, _f, _p, _i, _i, _f, _p]),
-    "rg_adam_hyper_dev3": (_i, [_p, _d, _d, _d, _d, _d, _p, _i, _p, _p]),
-    "rg_nonfinite_probe": (_i, [_i, _p, _p, _p, _p, _p]),
-    "rg_amp_update": (_i, [_p, _i, _i, _i, _i, _p]),
-    "rg_amp_latch": (_i, [_p, _i, _p]),
-    "rg_gp_coef_scaled_dev": (_i, [_p, _p, _p, _f, _p, _i, _p]),
-    "rg_gp_coef_parts_scaled_dev": (_i, [_p, _i, _p, _p, _p, _f, _p, _i, _p]),
-    "rg_head_bwd_data": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "rg_head_wgrad": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
-    "rg_pack_linear_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "rg_linear_workspace_bytes": (_z, [_i, _i, _i, _i]),
-    "rg_linear_affine_act": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_colreduce_workspace_bytes": (_z, [_i, _i, _i]),
-    "rg_bn_stats": (_i, [_p, _p, _p, _i, _i, _i, _p, _z, _p]),
-    "rg_bn_finalize": (_i, [_p, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p]),
-    "rg_bn_forward": (_i, [_p, _i, _i, _f, _f, _p, _p, _f, _p, _p, _p, _p, _p, _p, _i, _p, _z, _p]),
-    "rg_bn_forward_partials": (_i, [_p, _i, _p, _i, _i, _f, _f, _p, _p, _f, _p, _p, _p, _p, _p, _p, _i, _p, _z, _p]),
-    "rg_bn_stats_finalize": (_i, [_p, _i, _i, _f, _f, _p, _p, _p, _p, _p, _i, _p, _z, _p]),
-    "rg_bn_act": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p]),
-    "rg_bn_act_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_bn_act_bwd_g2": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_bn_finalize_partials": (_i, [_p, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "rg_linear_wgrad_adam": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _p, _i, _p]),
-    "rg_last_up_post_blocks": (_i, [_i, _i, _i, _i, _i, _i]),
-    "rg_last_up_post": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "rg_last_up_part_chan_sum": (_i, [_p, _i, _p, _i, _p]),
-    "rg_gp_coef_parts": (_i, [_p, _i, _p, _p, _p, _f, _p]),
-    "rg_last_up_pre_supported": (_i, [_i, _i, _i, _i]),
-    "rg_last_up_pre": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_bn_forward_g2": (_i, [_p, _i, _i, _p, _i, _i, _f, _f, _p, _p, _f, _p, _p, _p, _p, _p, _p, _i, _p, _z, _p]),
-    "rg_bn_finalize_partials_g2": (_i, [_p, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "rg_bn_tangent": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_bn_double_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i,
-                              _p, _z, _p]),
-    "rg_lrelu_bwd": (_i, [_p, _p, _p, _z, _f, _i, _p]),
-    "rg_col_sum": (_i, [_p, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_tanh_bwd": (_i, [_p, _p, _p, _z, _p]),
-    "rg_nchw_chan_sum": (_i, [_p, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_interp": (_i, [_p, _p, _p, _z, _f, _p]),
-    "rg_reduce_workspace_bytes": (_z, [_z]),
-    "rg_sqnorm": (_i, [_p, _p, _z, _p, _z, _p]),
-    "rg_gp_coef": (_i, [_p, _p, _p, _f, _p]),
-    "rg_scale_by": (_i, [_p, _p, _p, _z, _p]),
-    "rg_mean_diff": (_i, [_p, _p, _p, _i, _f, _p]),
-    "rg_latent_prep": (_i, [_p, _p, _p, _i, _i, _p]),
-    "rg_adam_step": (_i, [_p, _p, _p, _p, _z, _i, _d, _d, _d, _d, _p]),
-    "rg_clamp": (_i, [_p, _z, _f, _f, _p]),
-    "rg_upconv3_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
-    "rg_upconv3_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_upconv3_bwd_data": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_upconv3_wgrad": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_export_images_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "rg_bn_bwd_sums": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_bn_bwd_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p]),
-    "rg_bn_tangent_sums": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_bn_tangent_apply": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _p]),
-    "rg_bn_dbl_sums": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_bn_dbl_apply": (_i, [_p] * 17 + [_i, _i, _i, _i, _f, _i, _p, _z, _p]),
-    "rg_latent_stats": (_i, [_p, _p, _p, _p, _i, _i, _p]),
-    "rg_latent_apply": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
-    "rg_adam_step_dev": (_i, [_p, _p, _p, _p, _z, _p, _p, _p, _p]),
-    "rg_adam_step_slabs": (_i, [_p, _p, _p, _p, _z, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
-    "rg_ema_update": (_i, [_p, _p, _z, _f, _p, _p, _p]),
-    "rg_interp_dev": (_i, [_p, _p, _p, _z, _p, _p]),
-    "rg_adam_hyper_dev": (_i, [_p, _d, _d, _d, _d, _d, _p, _p]),
-    "rg_adam_hyper_dev2": (_i, [_p, _d, _d, _d, _d, _d, _d, _p, _p]),
-    "rg_storage_dtype": (_i, []),
-    "rg_gp_coef_scaled": (_i, [_p, _p, _p, _f, _f, _f, _p]),
-    "rg_gp_coef_parts_scaled": (_i, [_p, _i, _p, _p, _p, _f, _f, _f, _p]),
-    "rg_transpose_f32": (_i, [_p, _p, _i, _i, _p]),
-    "rg_transpose_pack_bf16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "rg_gemm_nt_bf16_workspace_bytes": (_z, [_i, _i, _i]),
-    "rg_gemm_nt_bf16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _z, _p]),
-    "rg_vae_dropout": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),
-    "rg_vae_reparam": (_i, [_p, _p, _p, _p, _z, _p]),
-    "rg_vae_reparam_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "rg_tanh_inplace": (_i, [_p, _z, _p]),
-    "rg_add_inplace": (_i, [_p, _p, _z, _p]),
-    "rg_vae_loss_workspace_bytes": (_z, []),
-    "rg_vae_loss": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _f, _i, _p, _p, _p, _p, _p, _z, _p]),
-    "rg_widen_bf16": (_i, [_p, _p, _z, _p]),
-    "rg_cast_pad": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "rg_selftest_layouts": (_i, [_p, _p]),
-    "rg_u8_to_norm": (_i, [_p, _p, _z, _f, _f, _p]),
-    "rg_tile_transform": (_i, [_p, _i, _p, _i, _i, _i, _p, _f, _f, _p]),
-    "rg_tile_gather_transform": (_i, [_p, C.c_longlong, _p, _p, _i, _i, _i, _p, _f, _f, _p]),
-    "rg_rows_gather_f32": (_i, [_p, C.c_longlong, _i, C.c_longlong, _p, _p, _i, C.c_longlong, _p]),
-    "rg_tile_export_u8": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _i, _p]),
-    "rg_tile_qc_workspace_bytes": (_z, [_i, _i, _i]),
-    "rg_tile_qc": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
-    "rg_window_resize_u8": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p]),
-    "rg_mask_erode": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "rg_box_reduce_u8": (_i, [_p, _i, _i, _i, _p, _p]),
-    "rg_stain_moments": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
-    "rg_stain_angle_hist": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _i, _p]),
-    "rg_stain_conc_hist": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _i, _p]),
-    "rg_stain_apply": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _p]),
-    "rg_tile_descriptor_i8": (_i, [_p, _i, _i, _i, _i, _p, C.c_longlong, _p, _p]),
-    "rg_nn_topk_ws_bytes": (_z, [_i, C.c_longlong, _i]),
-    "rg_nn_topk_i8": (_i, [_p, _p, _i, _p, _p, C.c_longlong, _i, C.c_longlong, _i, _p, _p, _p, _z, _p]),
-    "rg_msssim_plan": (_i, [_i, _i, _i, _i, _p, _p, _p]),
-    "rg_msssim_pyramid": (_i, [_p, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_msssim_pairs": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _z, _p, _p]),
-    "rg_conv_up_fp8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _f, _i, _p]),
-    "rg_gemm_fp8": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _f, _i, _p]),
-    "rg_fp8_supported": (_i, [_i, _i, _i, _i]),
-    "rg_cast_fp8": (_i, [_p, _p, _z, _f, _p]),
-    "rg_selftest_fp8": (_i, [_p, _p]),
-    "rg_g0_wgrad_adam_supported": (_i, [_i, _i, _i, _i]),
-    "rg_g0_wgrad_adam": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "rg_im2col_nhwc": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_pool2d_nhwc": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_nchw_to_nhwc_affine": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
-    "rg_spatial_mean_nhwc": (_i, [_p, _p, _i, _i, _i, _p]),
-    "rg_resize_bilinear01": (_i, [_p, _i, _l, _l, _l, _l, _f, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "rg_moments_update": (_i, [_p, _i, _i, _i, _p, _p, _p]),
-    "rg_polykernel_tile_sums": (_i, [_p, _i, _i, _p, _i, _i, _i, _d, _d, _i, _p, _p, _p]),
-    "rg_pairdist_ws_bytes": (_z, [_i, _i, _i]),
-    "rg_knn_radii2": (_i, [_p, _i, _i, _i, _i, _p, _z, _p, _p]),
-    "rg_radius_hits": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _z, _p, _p, _p]),
-    "rg_group_sums_update": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
-    "rg_match_ranks": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
-    "rg_linear_scores_f64": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _i, _p]),
-    "rg_softmax_residual_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
-    "rg_colsums_ws_bytes": (_z, [_i, _i, _i]),
-    "rg_rows_weighted_colsums_f64": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _z, _p, _p]),
-    "rg_conv_split": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_slab_dtype": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_down_partial": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_conv_up_partial": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_slab_bn_supported": (_i, [C.c_longlong, _i, _i, _i]),
-    "rg_slab_bn_scratch_bytes": (_z, [C.c_longlong, _i, _i]),
-    "rg_slab_bn_sync_words": (_z, []),
-    "rg_bn_forward_slabs": (_i, [_p, _i, _z, _i, _p, _p, C.c_longlong, _i, _i, _f, _f, _p, _p, _f, _p, _p, _p, _p, _p, _p, _z, _p, _p]),
-    "rg_bn_tangent_slabs": (_i, [_p, _i, _z, _i, _p, _p, _p, C.c_longlong, _i, _p, _p, _p, _p, _f, _p, _p, _p, _z, _p, _p]),
-    "rg_bn_act_bwd_slabs": (_i, [_p, _i, _z, _i, _p, _p, _p, C.c_longlong, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p, _z,
-                                 _p, _p]),
-    "rg_conv_up_affine": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _f, _p, _z, _p]),
-    "rg_g0_fwd_affine": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _f, _p, _z, _p]),
-    "rg_split_planes": (_i, [_p, _p, _z, _p]),
-    "rg_f32p_conv_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_f32p_conv_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_f32p_conv_stats_rows": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_f32p_conv": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _f, _p, _z, _p]),
-    "rg_f32p_conv_mask_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_f32p_wgrad_supported": (_i, [_i, _i, _i, _i, _i, _i]),
-    "rg_f32p_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_f32p_wgrad": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _z, _p]),
-    "rg_slab_finish_rows": (_i, [C.c_longlong, _i]),
-    "rg_slab_bias_act": (_i, [_p, _i, _z, _i, _p, _p, C.c_longlong, _i, _f, _p]),
-    "rg_slab_mask": (_i, [_p, _i, _z, _i, _p, _f, _p, _p, C.c_longlong, _i, _p]),
-    "rg_parts_col_sum": (_i, [_p, _i, _i, _p, _i, _p]),
-    "rg_bias_act": (_i, [_p, _p, _p, C.c_longlong, _i, _f, _i, _p]),
-    "rg_vec_sum": (_i, [_p, _i, _p, _i, _p]),
-    "rg_conv_down_epi_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "rg_conv_down_epi": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p, _f, _i, _i, _p, _z, _p]),
-    "rg_head_fwd_bias": (_i, [_p, _p, _p, _p, _p, _i, _i, _f, _i, _p]),
-    "rg_probe_mfma_bare": (_i, [_i, _i, _i, _i, _p, _p, _p]),
-    "rg_probe_lds_mfma": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
-    "rg_probe_copy": (_i, [_p, _p, _z, _i, _i, _p]),
-    "rg_probe_fill_bf16": (_i, [_p, _z, C.c_uint, _p]),
-    "rg_probe_window_resize_2pass": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _z, _p]),
-}
+def _ctype(text, named, decl):
+    """the ctypes type of one C parameter (``named``) or return type; anything but a pointer, an array or a _SCALARS type raises"""
+    words = text.replace("*", " * ").replace("[", " [ ").split()
+    if "*" in words or "[" in words:
+        return C.c_char_p if words[:3] == ["const", "char", "*"] and "*" not in words[3:] and "[" not in words else C.c_void_p
+    if named and (len(words) < 2 or words[-1] in _TYPE_WORDS):
+        raise ValueError("rnagan_hip.h: parameter %r without a name in: %s" % (text.strip(), decl))
+    ctype = _SCALARS.get(" ".join(w for w in (words[:-1] if named else words) if w != "const"))
+    if ctype is None:
+        raise ValueError("rnagan_hip.h: no ctypes mapping for %r in: %s" % (text.strip(), decl))
+    return ctype
 
-# must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped together with PROTOTYPES when an existing entry
-# point changes; an entry point that is only ADDED (rg_tile_transform, rg_tile_export_u8, rg_tile_qc, rg_tiler.hip's three, rg_tile_gather_transform, rg_rows_gather_f32, rg_groupstat.hip's two, rg_stain.hip's four, rg_nn.hip's three, rg_linprobe.hip's four, rg_msssim.hip's three) keeps the number -- load() refuses a library that lacks it
+
+def parse_header(text):
+    """(PROTOTYPES, CONSTANTS) of the header's text: every ``<ret> rg_name(<params>);`` as name -> (restype, [argtypes]) and every
+    ``#define RG_NAME <integer literal>`` as name -> int.  A use of an rg_ name that is not such a declaration raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {m.group(1): int(m.group(2).replace(" ", ""), 0) for m in re.finditer(
+        r"^[ \t]*#[ \t]*define[ \t]+(RG_\w+)[ \t]+\(?[ \t]*(-?[ \t]*(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    prototypes = {}
+    for m in re.finditer(r"([A-Za-z_][\w\s*]*?)\b(rg_\w+)\s*\(([^()]*)\)\s*;", text):
+        decl = " ".join(m.group(0).split())
+        if m.group(2) in prototypes:
+            raise ValueError("rnagan_hip.h: declared twice: %s" % decl)
+        params = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
+        prototypes[m.group(2)] = (_ctype(m.group(1), False, decl), [_ctype(p, True, decl) for p in params])
+    for name in re.findall(r"\b(rg_\w+)\s*\(", text):
+        if name not in prototypes:
+            raise ValueError("rnagan_hip.h: %s( is not a declaration of the form `<ret> rg_name(<params>);`" % name)
+    return prototypes, constants
+
+
+with open(HEADER_PATH) as _header:
+    PROTOTYPES, CONSTANTS = parse_header(_header.read())
+
+RG_F32, RG_BF16, RG_F16 = CONSTANTS["RG_F32"], CONSTANTS["RG_BF16"], CONSTANTS["RG_F16"]
+RG_U8 = CONSTANTS["RG_U8"]            # a source type only (rg_resize_bilinear01, rg_tile_transform)
+ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA = CONSTANTS["RG_ALGO_AUTO"], CONSTANTS["RG_ALGO_GENERIC"], CONSTANTS["RG_ALGO_MFMA"]
+
+# must equal rg_version() of the library (rna_gan_amd/csrc/rg_api.hip): bumped when an existing entry point changes; one that is
+# only ADDED keeps the number -- load() refuses a library that lacks it.  The one literal here: it has to disagree with a stale library
 ABI_VERSION = 618
 
 _libs = {}
@@ -285,13 +124,13 @@ def check(rc: int, what: str):
         raise RuntimeError("rna_gan_amd: %s failed (%d): %s" % (what, rc, " | ".join(msgs) if msgs else "?"))
 
 
-def launch(name: str, device, *args):
-    """One call of the bf16 library's entry point ``name``, whose LAST parameter is the stream: ``args`` are all the others, the
-    call is made with ``device`` current and on torch's current stream of it, and its return code is checked under ``name``.  A
-    small host operand goes in as a ctypes array where the prototype says c_void_p."""
+def launch(name: str, device, *args, half: str = "bf16"):
+    """One call of the entry point ``name`` of the ``half`` build, whose LAST parameter is the stream: ``args`` are all the others,
+    the call is made with ``device`` current and on torch's current stream of it, and its return code is checked under ``name``.
+    A small host operand goes in as a ctypes array where the prototype says c_void_p."""
     import torch
     with torch.cuda.device(device):
-        check(getattr(load(), name)(*args, torch.cuda.current_stream(device).cuda_stream), name)
+        check(getattr(load(half), name)(*args, torch.cuda.current_stream(device).cuda_stream), name)
 
 
 def device_key(device):

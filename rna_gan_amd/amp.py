@@ -22,10 +22,11 @@ import math
 
 import torch
 
-from ._abi import check, RG_F32
+from ._abi import check, CONSTANTS, RG_F32
 
-STATE_INTS = 12                          # include/rnagan_hip.h RG_AMP_*
-EXP, TRACKER, SKIPPED, LATCH, FLAG, SLOTS = 0, 1, 2, 4, 8, 4
+# include/rnagan_hip.h RG_AMP_*
+STATE_INTS, EXP, TRACKER, SKIPPED, LATCH, FLAG, SLOTS = (
+    CONSTANTS["RG_AMP_" + k] for k in ("STATE_INTS", "EXP", "TRACKER", "SKIPPED", "LATCH", "FLAG", "SLOTS"))
 PROBE_MAX_SEGS = 32
 
 

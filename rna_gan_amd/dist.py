@@ -216,9 +216,7 @@ def allreduce_start(flat: torch.Tensor, compress=False, head: int = 0, table=Non
     if compress and COMPRESS and flat.is_cuda and flat.dtype == torch.float32:
         from . import _abi
         half = _half_of(compress)
-        lib = _abi.load(half)
         wire = wire_for(flat, half)
-        stream = torch.cuda.current_stream(flat.device).cuda_stream
         if table:
             import ctypes as C
             k = len(table)
@@ -227,12 +225,11 @@ def allreduce_start(flat: torch.Tensor, compress=False, head: int = 0, table=Non
             slabs = (C.c_void_p * k)(*[t[2] or None for t in table])
             nsp = (C.c_int * k)(*[t[3] for t in table])
             sdts = (C.c_int * k)(*[t[4] for t in table])
-            _abi.check(lib.rg_grad_to_wire(flat.data_ptr() + 4 * head, wire.data_ptr() + 2 * head, n - head, k, C.addressof(offs),
-                                           C.addressof(lens), C.addressof(slabs), C.addressof(nsp), C.addressof(sdts), stream),
-                       "rg_grad_to_wire")
+            _abi.launch("rg_grad_to_wire", flat.device, flat.data_ptr() + 4 * head, wire.data_ptr() + 2 * head, n - head, k,
+                        C.addressof(offs), C.addressof(lens), C.addressof(slabs), C.addressof(nsp), C.addressof(sdts), half=half)
         else:
-            _abi.check(lib.rg_cast_pad(flat.data_ptr() + 4 * head, wire.data_ptr() + 2 * head, 1, n - head, n - head,
-                                       _abi.RG_F16 if half == "f16" else _abi.RG_BF16, stream), "rg_cast_pad")
+            _abi.launch("rg_cast_pad", flat.device, flat.data_ptr() + 4 * head, wire.data_ptr() + 2 * head, 1, n - head, n - head,
+                        _abi.RG_F16 if half == "f16" else _abi.RG_BF16, half=half)
         works = _launch_buckets(wire[head:], BUCKET_BYTES // 2)
         hog = _hog_start(flat.device) if flat.is_cuda else None
         return (wire, flat, works + ([_HogWork(hog)] if hog is not None else []), head)
@@ -252,9 +249,8 @@ def allreduce_finish(handle, widen=True):
         w.wait()
     if wire is not None and widen and flat.numel() > head:
         from . import _abi
-        stream = torch.cuda.current_stream(flat.device).cuda_stream
-        _abi.check(_abi.load("f16" if wire.dtype == torch.float16 else "bf16").rg_widen_bf16(wire.data_ptr() + 2 * head, flat.data_ptr() + 4 * head, flat.numel() - head, stream),
-                   "rg_widen_bf16")
+        _abi.launch("rg_widen_bf16", flat.device, wire.data_ptr() + 2 * head, flat.data_ptr() + 4 * head, flat.numel() - head,
+                    half="f16" if wire.dtype == torch.float16 else "bf16")
 
 
 def wire_of(handle):

@@ -23,7 +23,7 @@ import copy
 import torch
 
 from . import dist as D_
-from ._abi import check
+from . import _abi
 
 _RUNTIME_FIELDS = ("_rt_ops", "_rt_net", "_rt_flat", "_amp_scaler")
 
@@ -118,12 +118,12 @@ class ParamEMA:
         self._resolve()
         return True
 
-    def _launch(self, lib, hyper, step_dev, stream):
+    def _launch(self, half, hyper, step_dev):
         fs, ft = self.source._rt_flat, self.module._rt_flat
         if self._gens != (fs.gen, ft.gen):
             raise RuntimeError("ParamEMA: a module was re-homed between the optimizer's buffer check and its step")
-        check(lib.rg_ema_update(fs.data.data_ptr(), ft.data.data_ptr(), fs.numel, self._decay,
-                                step_dev.data_ptr() if self._warmup else None, hyper.data_ptr(), stream), "rg_ema_update")
+        _abi.launch("rg_ema_update", fs.data.device, fs.data.data_ptr(), ft.data.data_ptr(), fs.numel, self._decay,
+                    step_dev.data_ptr() if self._warmup else None, hyper.data_ptr(), half=half)
         self.module.weights_changed()              # plain version bump: no shadow was written
 
     # ------------------------------------------------------------------ on demand

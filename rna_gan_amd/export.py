@@ -27,7 +27,7 @@ import torch
 
 from . import _abi
 
-RG_EXPORT_PLANAR, RG_EXPORT_REVERSE, RG_EXPORT_TRUNC = 1, 2, 4
+RG_EXPORT_PLANAR, RG_EXPORT_REVERSE, RG_EXPORT_TRUNC = (_abi.CONSTANTS["RG_EXPORT_" + k] for k in ("PLANAR", "REVERSE", "TRUNC"))
 LAYOUTS = ("nhwc", "nchw")
 ORDERS = ("rgb", "bgr")
 ROUNDINGS = ("round", "trunc")

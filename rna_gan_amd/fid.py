@@ -199,10 +199,8 @@ def preprocess_images_device(images, size=299, value_range=None, layout=None):
         raise ValueError("expected 3 channels, got %d" % C)
     size = int(size)
     out = torch.empty((N, 3, size, size), dtype=torch.float32, device=images.device)
-    with torch.cuda.device(images.device):
-        stream = torch.cuda.current_stream(images.device).cuda_stream
-        _abi.check(_abi.load().rg_resize_bilinear01(images.data_ptr(), dtype, sn, sc, sh, sw, mul, add, out.data_ptr(), N, 3, H, W,
-                                                    size, size, stream), "rg_resize_bilinear01")
+    _abi.launch("rg_resize_bilinear01", images.device, images.data_ptr(), dtype, sn, sc, sh, sw, mul, add, out.data_ptr(), N, 3, H, W,
+                size, size)
     return out
 
 
@@ -231,10 +229,7 @@ class FeatureMoments:
             feats = feats.contiguous()
         n = feats.shape[0]
         ldx = feats.stride(0) if n > 1 else self.F
-        with torch.cuda.device(self.s1.device):
-            stream = torch.cuda.current_stream(self.s1.device).cuda_stream
-            _abi.check(_abi.load().rg_moments_update(feats.data_ptr(), ldx, n, self.F, self.s1.data_ptr(), self.s2.data_ptr(),
-                                                     stream), "rg_moments_update")
+        _abi.launch("rg_moments_update", self.s1.device, feats.data_ptr(), ldx, n, self.F, self.s1.data_ptr(), self.s2.data_ptr())
         self.n += n
         return self
 

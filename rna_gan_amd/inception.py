@@ -29,7 +29,6 @@ import torch
 import torch.nn as nn
 
 from . import _abi
-from ._abi import check
 
 # (name, cout, (kh, kw), (sh, sw), (ph, pw)) of every BasicConv2d of a block, and how the block wires them:
 #   ("conv", name, src)            src -> conv -> new buffer                    (src: "x" = block input or an earlier name)
@@ -167,8 +166,6 @@ class InceptionV3(nn.Module):
         dev = self.fc.weight.device
         if dev.type != "cuda":
             raise RuntimeError("InceptionV3.features runs on the HIP kernels only (move the module to a ROCm GPU)")
-        lib = _abi.load()
-        stream = torch.cuda.current_stream(dev).cuda_stream
         x01 = x01.to(dev).float().contiguous()
         N = x01.shape[0]
         # x * 2 - 1 (src/fid.py:55), then torchvision's transform_input: ch * (std_c / 0.5) + (mean_c - 0.5) / 0.5
@@ -176,8 +173,7 @@ class InceptionV3(nn.Module):
         mean = (torch.tensor([0.485, 0.456, 0.406], device=dev) - 0.5) / 0.5
         scale, shift = (2.0 * std).contiguous(), (mean - std).contiguous()
         x = torch.empty((N, 299, 299, 3), dtype=torch.float32, device=dev)
-        check(lib.rg_nchw_to_nhwc_affine(x01.data_ptr(), x.data_ptr(), N, 3, 299, 299, scale.data_ptr(), shift.data_ptr(),
-                                         stream), "rg_nchw_to_nhwc_affine")
+        _abi.launch("rg_nchw_to_nhwc_affine", dev, x01.data_ptr(), x.data_ptr(), N, 3, 299, 299, scale.data_ptr(), shift.data_ptr())
         scratch = {"buf": None}
 
         def cols_buf(nfloat):
@@ -199,17 +195,14 @@ class InceptionV3(nn.Module):
             a_ptr, lda = src.data_ptr() + 4 * c0, Csrc
             if (kh, kw, sh, sw, ph, pw) != (1, 1, 1, 1, 0, 0):
                 cols = cols_buf(M * K)
-                check(lib.rg_im2col_nhwc(a_ptr, Csrc, cols.data_ptr(), N, H, W, cin, kh, kw, sh, sw, ph, pw, stream),
-                      "rg_im2col_nhwc")
+                _abi.launch("rg_im2col_nhwc", dev, a_ptr, Csrc, cols.data_ptr(), N, H, W, cin, kh, kw, sh, sw, ph, pw)
                 a_ptr, lda = cols.data_ptr(), K
-            check(lib.rg_linear_affine_act(a_ptr, lda, wr.data_ptr(), 0, sc.data_ptr(), shf.data_ptr(),
-                                           dst.data_ptr() + 4 * d0, dst.shape[3], M, K, cout, 0.0, _abi.ALGO_GENERIC, 0, 0,
-                                           stream), "rg_linear_affine_act")
+            _abi.launch("rg_linear_affine_act", dev, a_ptr, lda, wr.data_ptr(), 0, sc.data_ptr(), shf.data_ptr(),
+                        dst.data_ptr() + 4 * d0, dst.shape[3], M, K, cout, 0.0, _abi.ALGO_GENERIC, 0, 0)
 
         def pool(src, k, s, p, mode, dst, d0):
             _, H, W, C = src.shape
-            check(lib.rg_pool2d_nhwc(src.data_ptr(), C, dst.data_ptr() + 4 * d0, dst.shape[3], N, H, W, C, k, s, p, mode,
-                                     stream), "rg_pool2d_nhwc")
+            _abi.launch("rg_pool2d_nhwc", dev, src.data_ptr(), C, dst.data_ptr() + 4 * d0, dst.shape[3], N, H, W, C, k, s, p, mode)
 
         def new(h, w, c):
             return torch.empty((N, h, w, c), dtype=torch.float32, device=dev)
@@ -257,7 +250,7 @@ class InceptionV3(nn.Module):
                 x = out
         assert tuple(x.shape[1:]) == (8, 8, 2048)
         feats = torch.empty((N, 2048), dtype=torch.float32, device=dev)
-        check(lib.rg_spatial_mean_nhwc(x.data_ptr(), feats.data_ptr(), N, 64, 2048, stream), "rg_spatial_mean_nhwc")
+        _abi.launch("rg_spatial_mean_nhwc", dev, x.data_ptr(), feats.data_ptr(), N, 64, 2048)
         return feats
 
     def forward(self, x01):

@@ -27,11 +27,6 @@ def _tiles(n):
     return (int(n) + TILE - 1) // TILE
 
 
-def _stream(device):
-    """torch's current stream on ``device``, as the entry points of the library take it"""
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _rows(x, what, dtype=torch.float32, no_columns=ValueError):
     """(tensor, row stride) of an (n, F) device tensor of ``dtype`` (float32 or float64) as the row kernels take it: unit column
     stride, row stride >= F; any other form is copied once (a row slice or a column slice of a wider tensor is NOT copied).
@@ -68,11 +63,9 @@ def _kernel_args(F, gamma, coef0, degree):
 def _launch(a, lda, b, ldb, gamma, coef0, degree, sums, diag):
     """one rg_polykernel_tile_sums launch on the current stream; sums / diag: contiguous fp64 views that receive the result"""
     from . import _abi
-    with torch.cuda.device(a.device):
-        rc = _abi.load().rg_polykernel_tile_sums(a.data_ptr(), lda, a.shape[0], None if b is None else b.data_ptr(), ldb,
-                                                 0 if b is None else b.shape[0], a.shape[1], gamma, coef0, degree,
-                                                 sums.data_ptr(), None if diag is None else diag.data_ptr(), _stream(a.device))
-        _abi.check(rc, "rg_polykernel_tile_sums")
+    _abi.launch("rg_polykernel_tile_sums", a.device, a.data_ptr(), lda, a.shape[0], None if b is None else b.data_ptr(), ldb,
+                0 if b is None else b.shape[0], a.shape[1], gamma, coef0, degree, sums.data_ptr(),
+                None if diag is None else diag.data_ptr())
 
 
 def polykernel_tile_sums(a, b=None, gamma=None, coef0=1.0, degree=3):

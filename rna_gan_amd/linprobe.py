@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .kid import _rows, _stream
+from .kid import _rows
 
 FOLD_STREAM = 0xC257         # second word of the fold generator's seed: default_rng([seed, FOLD_STREAM])
 
@@ -183,39 +183,37 @@ class _DeviceOps:
         self.x, self.ldx, self.C = x, ldx, C
         self.n, self.F = x.shape
         n, F, dev = self.n, self.F, x.device
-        self.lib = _abi.load()
         f64 = dict(dtype=torch.float64, device=dev)
         self.z, self.resid, self.row_loss = torch.empty(n, C, **f64), torch.empty(n, C, **f64), torch.empty(n, **f64)
         self.ones = torch.ones(n, 1, dtype=torch.float32, device=dev)
         self.params = torch.empty(C * F + C, **f64)
         self.out = torch.empty(max(C * F + C + 1, 2 * F), **f64)
-        need = max(self.lib.rg_colsums_ws_bytes(n, F, C), self.lib.rg_colsums_ws_bytes(n, 1, C))
+        ws_bytes = _abi.load().rg_colsums_ws_bytes
+        need = max(ws_bytes(n, F, C), ws_bytes(n, 1, C))
         self.ws = torch.empty(max(need, 8) // 8, **f64)
         self.label = torch.full((n,), -1, dtype=torch.int32, device=dev)       # until set_rows: every row left out
         self.weight, self.weighted = torch.empty(n, **f64), False
 
     def _colsums(self, x, ldx, F, r, ldr, C, power, out):
-        _abi.check(self.lib.rg_rows_weighted_colsums_f64(x.data_ptr(), ldx, self.n, F, r.data_ptr(), ldr, C, power, self.ws.data_ptr(),
-                                                         self.ws.numel() * 8, out.data_ptr(), _stream(self.x.device)),
-                   "rg_rows_weighted_colsums_f64")
+        _abi.launch("rg_rows_weighted_colsums_f64", self.x.device, x.data_ptr(), ldx, self.n, F, r.data_ptr(), ldr, C, power,
+                    self.ws.data_ptr(), self.ws.numel() * 8, out.data_ptr())
 
     def moments(self, mask01):
         F = self.F
-        with torch.cuda.device(self.x.device):
-            r = torch.from_numpy(np.ascontiguousarray(mask01, dtype=np.float64)).to(self.x.device)
-            self._colsums(self.x, self.ldx, F, r, 1, 1, 1, self.out[:F])
-            self._colsums(self.x, self.ldx, F, r, 1, 1, 2, self.out[F:2 * F])
-            host = self.out[:2 * F].cpu().numpy()
+        r = torch.from_numpy(np.ascontiguousarray(mask01, dtype=np.float64)).to(self.x.device)
+        self._colsums(self.x, self.ldx, F, r, 1, 1, 1, self.out[:F])
+        self._colsums(self.x, self.ldx, F, r, 1, 1, 2, self.out[F:2 * F])
+        host = self.out[:2 * F].cpu().numpy()
         return host[:F].copy(), host[F:].copy()
 
     def logits(self, W, b):
         """z = x W^T + b into self.z (the (n, C) fp64 device buffer of this object)"""
-        C, F, st = self.C, self.F, _stream(self.x.device)
+        C, F = self.C, self.F
         self.params.copy_(torch.from_numpy(np.concatenate([np.ascontiguousarray(W, dtype=np.float64).reshape(-1),
                                                            np.ascontiguousarray(b, dtype=np.float64)])))
         p = self.params.data_ptr()
-        _abi.check(self.lib.rg_linear_scores_f64(self.x.data_ptr(), self.ldx, self.n, F, p, F, C, p + 8 * C * F, self.z.data_ptr(), C,
-                                                 st), "rg_linear_scores_f64")
+        _abi.launch("rg_linear_scores_f64", self.x.device, self.x.data_ptr(), self.ldx, self.n, F, p, F, C, p + 8 * C * F,
+                    self.z.data_ptr(), C)
         return self.z
 
     def set_rows(self, label, weight):
@@ -226,16 +224,14 @@ class _DeviceOps:
             self.weight.copy_(torch.from_numpy(np.ascontiguousarray(weight, dtype=np.float64)))
 
     def evaluate(self, W, b):
-        C, F, n, st = self.C, self.F, self.n, _stream(self.x.device)
-        with torch.cuda.device(self.x.device):
-            self.logits(W, b)
-            _abi.check(self.lib.rg_softmax_residual_f64(self.z.data_ptr(), C, n, C, self.label.data_ptr(),
-                                                        self.weight.data_ptr() if self.weighted else None, self.resid.data_ptr(), C,
-                                                        self.row_loss.data_ptr(), st), "rg_softmax_residual_f64")
-            self._colsums(self.x, self.ldx, F, self.resid, C, C, 1, self.out[:C * F])
-            self._colsums(self.ones, 1, 1, self.resid, C, C, 1, self.out[C * F:C * F + C])
-            self._colsums(self.ones, 1, 1, self.row_loss, 1, 1, 1, self.out[C * F + C:C * F + C + 1])
-            host = self.out[:C * F + C + 1].cpu().numpy()
+        C, F, n = self.C, self.F, self.n
+        self.logits(W, b)
+        _abi.launch("rg_softmax_residual_f64", self.x.device, self.z.data_ptr(), C, n, C, self.label.data_ptr(),
+                    self.weight.data_ptr() if self.weighted else None, self.resid.data_ptr(), C, self.row_loss.data_ptr())
+        self._colsums(self.x, self.ldx, F, self.resid, C, C, 1, self.out[:C * F])
+        self._colsums(self.ones, 1, 1, self.resid, C, C, 1, self.out[C * F:C * F + C])
+        self._colsums(self.ones, 1, 1, self.row_loss, 1, 1, 1, self.out[C * F + C:C * F + C + 1])
+        host = self.out[:C * F + C + 1].cpu().numpy()
         return host[:C * F].reshape(C, F).copy(), host[C * F:C * F + C].copy(), float(host[C * F + C])
 
 
@@ -302,10 +298,8 @@ def scores(probe, x):
     n, F, C = x.shape[0], x.shape[1], probe.W.shape[0]
     z = torch.empty(n, C, dtype=torch.float64, device=x.device)
     params = torch.from_numpy(np.concatenate([probe.W.reshape(-1), probe.b]).astype(np.float64)).to(x.device)
-    with torch.cuda.device(x.device):
-        p = params.data_ptr()
-        _abi.check(_abi.load().rg_linear_scores_f64(x.data_ptr(), ldx, n, F, p, F, C, p + 8 * C * F, z.data_ptr(), C, _stream(x.device)),
-                   "rg_linear_scores_f64")
+    p = params.data_ptr()
+    _abi.launch("rg_linear_scores_f64", x.device, x.data_ptr(), ldx, n, F, p, F, C, p + 8 * C * F, z.data_ptr(), C)
     return z
 
 

@@ -32,7 +32,7 @@ import torch
 from . import _abi
 from .export import export_flags, tile_args
 
-BAND, COLS = 32, 16                  # window positions per workgroup (RG_MSSSIM_BAND x RG_MSSSIM_COLS of include/rnagan_hip.h)
+BAND, COLS = _abi.CONSTANTS["RG_MSSSIM_BAND"], _abi.CONSTANTS["RG_MSSSIM_COLS"]      # window positions per workgroup
 TAPS, SIGMA = 11, 1.5
 C1, C2 = (0.01 * 255.0) ** 2, (0.03 * 255.0) ** 2
 WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)

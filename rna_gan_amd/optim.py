@@ -334,7 +334,7 @@ class Adam(torch.optim.Adam):
             fn()
         if self._ema is not None:
             # the average of the parameters just written: same stream, same step counter (warm-up) and skip word
-            self._ema._launch(lib, self._hyper, self._step_dev, stream)
+            self._ema._launch(getattr(mops, "half", "bf16"), self._hyper, self._step_dev)
         if amp is not None:
             amp.update(lib, self._module, stream)
         if not torch.cuda.is_current_stream_capturing():

@@ -22,14 +22,14 @@ from __future__ import annotations
 import torch
 
 from . import _abi
-from .kid import _row_pair, _rows, _stream
+from .kid import _row_pair, _rows
 
 KMAX = 16
 _WS = {}            # device -> the cached workspace (one uint8 buffer per device, grown on demand)
 
 
 def _workspace(device, nbytes):
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    key = _abi.device_key(device)
     ws = _WS.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = _WS[key] = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
@@ -51,12 +51,9 @@ def knn_radii2(x, k):
     x, ldx = _rows(x, "x")
     n, F = x.shape
     k = _check_k(k, n, "x")
-    lib = _abi.load()
-    ws = _workspace(x.device, lib.rg_pairdist_ws_bytes(n, n, k))
+    ws = _workspace(x.device, _abi.load().rg_pairdist_ws_bytes(n, n, k))
     r2 = torch.empty(n, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _abi.check(lib.rg_knn_radii2(x.data_ptr(), ldx, n, F, k, ws.data_ptr(), ws.numel(), r2.data_ptr(), _stream(x.device)),
-                   "rg_knn_radii2")
+    _abi.launch("rg_knn_radii2", x.device, x.data_ptr(), ldx, n, F, k, ws.data_ptr(), ws.numel(), r2.data_ptr())
     return r2
 
 
@@ -72,14 +69,11 @@ def radius_hits(a, b, rb2=None):
         if not (torch.is_tensor(rb2) and rb2.dtype == torch.float64 and rb2.device == a.device and rb2.shape == (nb,)):
             raise ValueError("rb2 must be an (nb,) float64 tensor on the device of a and b")
         rb2 = rb2.contiguous()
-    lib = _abi.load()
-    ws = _workspace(a.device, lib.rg_pairdist_ws_bytes(na, nb, 0))
+    ws = _workspace(a.device, _abi.load().rg_pairdist_ws_bytes(na, nb, 0))
     count = None if rb2 is None else torch.empty(na, dtype=torch.int32, device=a.device)
     mind2 = torch.empty(na, dtype=torch.float64, device=a.device)
-    with torch.cuda.device(a.device):
-        _abi.check(lib.rg_radius_hits(a.data_ptr(), lda, na, b.data_ptr(), ldb, nb, F, None if rb2 is None else rb2.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), None if count is None else count.data_ptr(), mind2.data_ptr(),
-                                      _stream(a.device)), "rg_radius_hits")
+    _abi.launch("rg_radius_hits", a.device, a.data_ptr(), lda, na, b.data_ptr(), ldb, nb, F, None if rb2 is None else rb2.data_ptr(),
+                ws.data_ptr(), ws.numel(), None if count is None else count.data_ptr(), mind2.data_ptr())
     return count, mind2
 
 

@@ -14,7 +14,6 @@ import time
 import torch
 
 from . import _abi
-from ._abi import check
 
 
 def _timed(launch, settle_s: float, n_timed: int, device):
@@ -41,8 +40,6 @@ def _timed(launch, settle_s: float, n_timed: int, device):
 def measure_ceilings(device, settle_s: float = 2.0, n_timed: int = 8, copy_mb: int = 1024):
     """{name: value}: TFLOP/s of the bare bf16 MFMA loops (both shapes, one and two waves per SIMD), TFLOP/s of the product's
     8-wave conv k-loop fed from LDS-resident stages (both shapes), GB/s of a float4 stream copy (read + write bytes)."""
-    lib = _abi.load()
-    st = torch.cuda.current_stream(device).cuda_stream
     out = {"protocol": "random operands; %.1f s of back-to-back launches of the same kernel, then %d timed launches (one HIP "
                        "event pair on the launch stream)" % (settle_s, n_timed)}
     scratch = torch.zeros(64, dtype=torch.float32, device=device)
@@ -52,32 +49,30 @@ def measure_ceilings(device, settle_s: float = 2.0, n_timed: int = 8, copy_mb: i
         for wps in (1, 2):
             iters = 40000 // wps          # ~20-40 ms per launch
             def launch(shape=shape, wps=wps, iters=iters):
-                check(lib.rg_probe_mfma_bare(shape, wps, ncu, iters, scratch.data_ptr(), ctypes.addressof(fl), st),
-                      "rg_probe_mfma_bare")
+                _abi.launch("rg_probe_mfma_bare", device, shape, wps, ncu, iters, scratch.data_ptr(), ctypes.addressof(fl))
             ms = _timed(launch, settle_s, n_timed, device)
             out["mfma_bare_%s_%dwave_tflops" % ("16x16x32" if shape == 16 else "32x32x16", wps)] = round(fl.value / (ms * 1e-3) / 1e12, 1)
     a = torch.empty((ncu * 256, 128), dtype=torch.bfloat16, device=device)
     b = torch.empty((256, 128), dtype=torch.bfloat16, device=device)
     c = torch.empty((ncu * 256, 256), dtype=torch.bfloat16, device=device)
-    check(lib.rg_probe_fill_bf16(a.data_ptr(), a.numel(), 11, st), "rg_probe_fill_bf16")
-    check(lib.rg_probe_fill_bf16(b.data_ptr(), b.numel(), 23, st), "rg_probe_fill_bf16")
+    _abi.launch("rg_probe_fill_bf16", device, a.data_ptr(), a.numel(), 11)
+    _abi.launch("rg_probe_fill_bf16", device, b.data_ptr(), b.numel(), 23)
     for shape in (16, 32):
         iters = 16384                      # k-tiles per workgroup: ~15-25 ms per launch
         def launch(shape=shape, iters=iters):
-            check(lib.rg_probe_lds_mfma(shape, ncu, iters, a.data_ptr(), b.data_ptr(), c.data_ptr(), ctypes.addressof(fl), st),
-                  "rg_probe_lds_mfma")
+            _abi.launch("rg_probe_lds_mfma", device, shape, ncu, iters, a.data_ptr(), b.data_ptr(), c.data_ptr(), ctypes.addressof(fl))
         ms = _timed(launch, settle_s, n_timed, device)
         out["conv8_loop_lds_fed_%s_tflops" % ("16x16x32" if shape == 16 else "32x32x16")] = round(fl.value / (ms * 1e-3) / 1e12, 1)
     del a, b, c
     nbytes = copy_mb << 20
     src = torch.empty(nbytes, dtype=torch.uint8, device=device)
     dst = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    check(lib.rg_probe_fill_bf16(src.data_ptr(), nbytes // 2, 5, st), "rg_probe_fill_bf16")
+    _abi.launch("rg_probe_fill_bf16", device, src.data_ptr(), nbytes // 2, 5)
 
     best = None
     for variant, blocks in ((0, 2048), (1, 2048), (0, 4096), (1, 4096)):
         def launch_copy(variant=variant, blocks=blocks):
-            check(lib.rg_probe_copy(src.data_ptr(), dst.data_ptr(), nbytes, variant, blocks, st), "rg_probe_copy")
+            _abi.launch("rg_probe_copy", device, src.data_ptr(), dst.data_ptr(), nbytes, variant, blocks)
         ms = _timed(launch_copy, min(settle_s, 0.5), n_timed, device)
         gbps = round(2.0 * nbytes / (ms * 1e-3) / 1e9, 1)
         out["stream_copy_%s_%d_gbps" % ("nt" if variant else "plain", blocks)] = gbps

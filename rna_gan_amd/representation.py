@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .kid import _row_pair, _rows, _stream
+from .kid import _row_pair, _rows
 
 
 class GroupMeans:
@@ -50,10 +50,8 @@ class GroupMeans:
         if not (torch.is_tensor(group) and group.dtype == torch.int32 and group.device == feats.device and tuple(group.shape) == (n,)):
             raise TypeError("GroupMeans.update takes the group ids as an (n,) int32 tensor on the features' device")
         group = group.contiguous()
-        with torch.cuda.device(self.sums.device):
-            _abi.check(_abi.load().rg_group_sums_update(feats.data_ptr(), ldx, n, self.F, group.data_ptr(), self.G, self.sums.data_ptr(),
-                                                        self._counts.data_ptr(), _stream(self.sums.device)),
-                       "rg_group_sums_update")
+        _abi.launch("rg_group_sums_update", self.sums.device, feats.data_ptr(), ldx, n, self.F, group.data_ptr(), self.G,
+                    self.sums.data_ptr(), self._counts.data_ptr())
         self.n += n
         return self
 
@@ -118,10 +116,8 @@ def match_ranks(query, ref, target=None, center=True):
         lda = ldb = F
     rank = torch.empty(na, dtype=torch.int32, device=query.device)
     dtarget = torch.empty(na, dtype=torch.float64, device=query.device)
-    with torch.cuda.device(query.device):
-        _abi.check(_abi.load().rg_match_ranks(query.data_ptr(), lda, na, ref.data_ptr(), ldb, nb, F,
-                                              None if target is None else target.data_ptr(), rank.data_ptr(), dtarget.data_ptr(),
-                                              _stream(query.device)), "rg_match_ranks")
+    _abi.launch("rg_match_ranks", query.device, query.data_ptr(), lda, na, ref.data_ptr(), ldb, nb, F,
+                None if target is None else target.data_ptr(), rank.data_ptr(), dtarget.data_ptr())
     return rank, dtarget
 
 
@@ -136,6 +132,14 @@ def retrieval_scores(rank, n_ref):
         raise ValueError("retrieval_scores takes at least one rank and n_ref >= 1")
     return {"top1": float(np.mean(r == 0)), "top5": float(np.mean(r < min(5, n_ref))), "mrr": float(np.mean(1.0 / (r + 1.0))),
             "median_rank": float(np.median(r)), "chance_top1": 1.0 / n_ref}
+
+
+def latent_prep(u, z):
+    """u + z standardised per column over the rows handed in (rg_latent_prep), u and z contiguous (n, E) fp32 on one device:
+    the rank-local form, no collective (HipOps.latent_prep has the one with synchronised statistics)"""
+    out = torch.empty_like(u)
+    _abi.launch("rg_latent_prep", u.device, u.data_ptr(), z.data_ptr(), out.data_ptr(), u.shape[0], u.shape[1])
+    return out
 
 
 def conditioned_noise(generator, betavae, gene_exp, tiles_per_patient, seed, group=4096):
@@ -158,15 +162,7 @@ def conditioned_noise(generator, betavae, gene_exp, tiles_per_patient, seed, gro
     if group < 2:
         raise ValueError("group must be at least 2")
     device = next(generator.parameters()).device
-    if hasattr(generator, "runtime"):
-        latent_prep = generator.runtime()[0].latent_prep
-    else:
-        def latent_prep(u, z):
-            out = torch.empty_like(u)
-            with torch.cuda.device(device):
-                _abi.check(_abi.load().rg_latent_prep(u.data_ptr(), z.data_ptr(), out.data_ptr(), u.shape[0], u.shape[1],
-                                                      _stream(device)), "rg_latent_prep")
-            return out
+    prep = generator.runtime()[0].latent_prep if hasattr(generator, "runtime") else latent_prep
     betavae = betavae.to(device)
     was_training = betavae.training
     betavae.eval()
@@ -180,7 +176,7 @@ def conditioned_noise(generator, betavae, gene_exp, tiles_per_patient, seed, gro
         patient = (torch.arange(r0, r1) % P).to(device)
         u = torch.empty(r1 - r0, generator.encoding_dims).uniform_(-0.3, 0.3, generator=private).to(device)
         with torch.no_grad():
-            noise = latent_prep(u.contiguous(), z[patient].contiguous())
+            noise = prep(u.contiguous(), z[patient].contiguous())
         yield patient.to(torch.int32), noise
 
 
@@ -191,9 +187,7 @@ def _real_batch(x, resize, mean, std):
         return x if x.dtype == torch.uint8 else x.float()
     x = x.contiguous()
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _abi.check(_abi.load().rg_u8_to_norm(x.data_ptr(), y.data_ptr(), x.numel(), float(mean), float(std), _stream(x.device)),
-                   "rg_u8_to_norm")
+    _abi.launch("rg_u8_to_norm", x.device, x.data_ptr(), y.data_ptr(), x.numel(), float(mean), float(std))
     return y
 
 
