@@ -26,7 +26,6 @@ import os
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 FLAGS = [
     ("--config", str, None, "the training run's JSON config (path_csv, patch_data_path, img_size)"),
@@ -61,57 +60,26 @@ def parse_args(argv=None):
                 ap.error("--%s is required without --synthetic" % flag)
     if args.samples < 1:
         ap.error("--samples must be >= 1")
-    if args.factor not in (1, 2, 4, 8, 16, 32):
+    from rna_gan_amd.gan_utils import check_flags
+    from rna_gan_amd.nearest import FACTORS
+    if args.factor not in FACTORS:
         ap.error("--factor must be 1, 2, 4, 8, 16 or 32")
     if not 1 <= args.k <= 8:
         ap.error("--k must be in 1..8")
-    for flag in ("d4", "g_ema"):
-        if getattr(args, flag) not in (0, 1):
-            ap.error("--%s must be 0 or 1" % flag)
-    if args.precision not in ("bf16", "fp16", "fp32"):
-        ap.error("--precision must be bf16, fp16 or fp32")
+    check_flags(ap, args, binary=("d4", "g_ema"))
     if args.num_patches < 1 or args.img_size < 1 or args.synthetic_tiles < 2:
         ap.error("--num_patches and --img_size must be positive, --synthetic_tiles at least 2")
     return args
 
 
-def build_models(args, device):
-    """(trainer, betavae or None) from the files, or a seeded random generator under --synthetic."""
-    import rna_gan_amd as P
-    from rna_gan_amd import synth
-    from rna_gan_amd.gan_utils import load_torchgan_trainer
-    if args.synthetic:
-        from types import SimpleNamespace
-        if args.g_ema:
-            raise SystemExit("--g_ema 1 needs a checkpoint")
-        G = P.DCGANGenerator(2048, args.img_size, 3, 64, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.Tanh())
-        synth.seeded_fill_(G, args.seed + 2)
-        return SimpleNamespace(generator=G.set_precision(args.precision).to(device), device=device), None
-    trainer = load_torchgan_trainer(args.checkpoint, device=str(device), precision=args.precision, ema_decay=0.999 if args.g_ema else None)
-    bv = None
-    if args.vae_checkpoint:
-        bv = P.betaVAE(args.rna_features, 2048, [6000, 4000, 2048], [4000, 6000], beta=0.0005)
-        bv.load_checkpoint_file(args.vae_checkpoint)
-        bv = bv.set_precision(args.precision).eval()
-    return trainer, bv
-
-
 def training_set(args, config, device, with_rna):
     """The training tiles as a resident.DeviceTileSet (with the slides' expression rows when the generator is conditioned)."""
-    from rna_gan_amd.resident import DeviceTileSet
     if args.synthetic:
+        from rna_gan_amd.resident import DeviceTileSet
         from rna_gan_amd.synth import synthetic_tiles_u8
         return DeviceTileSet.from_tensors(synthetic_tiles_u8(args.synthetic_tiles, args.img_size, args.seed + 1), device=device)
-    import random
-    from rna_gan_amd import data as PD
-    random.seed(args.seed)                                  # the datasets draw their per-slide tile sample from `random`
-    df = PD.load_slide_tables(config["path_csv"], config["patch_data_path"])
-    if with_rna:
-        df = PD.log_standardize_rna(df)[0]
-        ds = PD.PatchRNADataset(config["patch_data_path"], df, config["img_size"], max_patches_total=args.num_patches, transforms=None)
-    else:
-        ds = PD.PatchDataset(config["patch_data_path"], df, config["img_size"], max_patches_total=args.num_patches, transforms=None)
-    return DeviceTileSet.from_dataset(ds, device, workers=4)
+    from rna_gan_amd.gan_utils import resident_training_set
+    return resident_training_set(config, args.seed, args.num_patches, device, with_rna=with_rna, workers=4)
 
 
 def generated_tiles(args, trainer, betavae, ts, device):
@@ -158,6 +126,7 @@ def run(args, trainer=None, betavae=None, tile_set=None):
             config = json.load(f)
         args.rna_features = int(config.get("rna_features", args.rna_features))
     if trainer is None:
+        from rna_gan_amd.gan_utils import build_models
         trainer, betavae = build_models(args, device)
     ts = tile_set if tile_set is not None else training_set(args, config, device, betavae is not None)
     if betavae is not None and ts.rna is None:

@@ -28,7 +28,6 @@ import os
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 import rna_gan_amd as P
 
@@ -58,37 +57,9 @@ def parse_args(argv=None):
     return args
 
 
-def _synthetic_inputs(args, config, device):
-    """(tile set, generator, discriminator, betaVAE, unconditioned generator or None), all seeded"""
-    from rna_gan_amd import synth
-    from rna_gan_amd.resident import DeviceTileSet
-    size, features = int(config["img_size"]), int(config.get("rna_features", 19198))
-    patients, enc = int(config.get("synthetic_patients", 8)), int(config.get("encoding_dims", 64))
-    step = int(config.get("step_channels", 4))
-    n = patients * args.sample_size
-    ts = DeviceTileSet.from_tensors(synth.synthetic_tiles_u8(n, size, args.seed), rna=synth.synthetic_rna(patients, features, args.seed + 1,
-                                                                                                            distinct=patients),
-                                    row_of=torch.arange(n, dtype=torch.int32) % patients, device=device)
-
-    def generator(seed):
-        g = P.DCGANGenerator(enc, size, 3, step, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.Tanh())
-        return synth.seeded_fill_(g, seed).to(device)
-    D = synth.seeded_fill_(P.DCGANDiscriminator(size, 3, step, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.LeakyReLU(0.2)),
-                           args.seed + 3).to(device)
-    bv = synth.seeded_fill_(P.betaVAE(features, enc, [40, 36, enc], [36, 40], beta=0.0005), args.seed + 4).to(device)
-    return ts, generator(args.seed + 2), D, bv, (generator(args.seed + 5) if args.gan is not None else None)
-
-
 def _file_inputs(args, config, device):
-    import random
-    from rna_gan_amd import data as PD
-    from rna_gan_amd.gan_utils import load_torchgan_trainer
-    from rna_gan_amd.resident import DeviceTileSet
-    random.seed(args.seed)                                  # the per-slide key sample is drawn from the global ``random`` generator
-    table = PD.load_slide_tables(config["path_csv"], config["patch_data_path"])
-    table, _, _ = PD.log_standardize_rna(table)
-    ds = PD.PatchRNADataset(config["patch_data_path"], table, config["img_size"], max_patches_total=args.sample_size, transforms=None)
-    ts = DeviceTileSet.from_dataset(ds, device)             # unreadable records are dropped here, once
+    from rna_gan_amd.gan_utils import load_torchgan_trainer, resident_training_set
+    ts = resident_training_set(config, args.seed, args.sample_size, device)
     print("Real tiles on {}: {} tiles of {} patients, {} unreadable records skipped".format(device, len(ts), ts.rna.shape[0], ts.dropped))
     features = int(config.get("rna_features", ts.rna.shape[1]))
     bv = P.betaVAE(features, 2048, [6000, 4000, 2048], [4000, 6000], beta=0.0005)
@@ -101,17 +72,18 @@ def _file_inputs(args, config, device):
 def run(args):
     """The three (two without --gan) sets of centroids as (P, F) fp64 device tensors under "real", "conditioned" and
     "unconditioned"; writes the .npy files and prints the retrieval scores."""
-    from rna_gan_amd import fid as FID
     from rna_gan_amd import representation as RP
+    from rna_gan_amd import synth
+    from rna_gan_amd.metrics import feature_extractor
     with open(args.config) as f:
         config = json.load(f)
     print(10 * "-"); print("Config for this experiment \n"); print(config); print(10 * "-")
     device = torch.device("cuda:0")
-    ts, G, D, bv, gan = (_synthetic_inputs if args.synthetic else _file_inputs)(args, config, device)
-    if args.extractor == "discriminator":
-        extract, resize = FID.discriminator_features_device(D), None
+    if args.synthetic:
+        ts, G, D, bv, gan = synth.evaluation_inputs(config, args.sample_size, args.seed, device, second_generator=args.gan is not None)
     else:
-        extract, resize = FID.inception_features_device(args.extractor, device), 299
+        ts, G, D, bv, gan = _file_inputs(args, config, device)
+    extract, resize = feature_extractor(args.extractor, D, device)
     reps = RP.patient_representations(extract, real=ts, conditioned=G, unconditioned=gan, betavae=bv, gene_exp=ts.rna,
                                       tiles_per_patient=args.sample_size, seed=args.seed, resize=resize)
     for key, name in (("real", "real"), ("conditioned", "vaegan"), ("unconditioned", "gan")):

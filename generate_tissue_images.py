@@ -40,7 +40,6 @@ import sys
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 REFERENCE_FLAGS = [
     ("--config", str, None, "JSON config file (optional here: rna_features / img_size are read from it when present)"),
@@ -119,15 +118,12 @@ def parse_args(argv=None):
                 ap.error("--%s is required without --synthetic" % flag)
     if args.quantize not in ("round", "trunc"):
         ap.error("--quantize must be round or trunc")
-    for flag in ("prepare_rna", "g_ema", "fp8"):
-        if getattr(args, flag) not in (0, 1):
-            ap.error("--%s must be 0 or 1" % flag)
+    from rna_gan_amd.gan_utils import check_flags
+    check_flags(ap, args, binary=("prepare_rna", "g_ema", "fp8"))
     if args.chunk < 1:
         ap.error("--chunk must be >= 1")
     if args.group < 2:
         ap.error("--group must be >= 2")
-    if args.precision not in ("bf16", "fp16", "fp32"):
-        ap.error("--precision must be bf16, fp16 or fp32")
     if args.fp8 and args.precision != "bf16":
         ap.error("--fp8 1 needs --precision bf16")
     if args.rna_features < 1 or args.img_size < 1:
@@ -170,29 +166,6 @@ def select_patients(spec, ids):
     return rows
 
 
-def build_models(args, device):
-    """(trainer, betavae) from the files, or seeded random ones under --synthetic."""
-    import rna_gan_amd as P
-    from rna_gan_amd import synth
-    from rna_gan_amd.gan_utils import load_torchgan_trainer
-    if args.synthetic:
-        from types import SimpleNamespace
-        G = P.DCGANGenerator(2048, args.img_size, 3, 64, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.Tanh())
-        synth.seeded_fill_(G, args.seed + 2)
-        G = G.set_precision(args.precision).to(device)
-        if args.g_ema:
-            raise SystemExit("--g_ema 1 needs a checkpoint")
-        trainer = SimpleNamespace(generator=G, device=device)
-        bv = P.betaVAE(args.rna_features, 2048, [6000, 4000, 2048], [4000, 6000], beta=0.0005)
-        synth.seeded_fill_(bv, args.seed + 3)
-    else:
-        trainer = load_torchgan_trainer(args.checkpoint, device=str(device), precision=args.precision,
-                                        ema_decay=0.999 if args.g_ema else None)
-        bv = P.betaVAE(args.rna_features, 2048, [6000, 4000, 2048], [4000, 6000], beta=0.0005)
-        bv.load_checkpoint_file(args.vae_checkpoint)
-    return trainer, bv.set_precision(args.precision).eval()
-
-
 def compose_grid(tiles, rows=8, cols=8):
     """(n, H, W, 3) uint8, n <= rows * cols -> one (rows * H, cols * W, 3) uint8 image, row-major, unused cells black."""
     n, H, W, C = tiles.shape
@@ -208,9 +181,9 @@ def run(args, trainer=None, betavae=None):
     list of paths written."""
     from PIL import Image
     from rna_gan_amd.data import write_tile_store
-    from rna_gan_amd.gan_utils import generate_tiles
+    from rna_gan_amd.gan_utils import build_models, generate_tiles
     if trainer is None or betavae is None:
-        trainer, betavae = build_models(args, torch.device("cuda", 0))
+        trainer, betavae = build_models(args, torch.device("cuda", 0), synthetic_betavae=True)
     ids, rows = load_rna(args)
     common = dict(seed=args.seed, ema=bool(args.g_ema), fp8=bool(args.fp8), chunk=args.chunk, group=args.group,
                   layout="nhwc", order="rgb", rounding=args.quantize)

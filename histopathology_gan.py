@@ -171,10 +171,12 @@ def parse_args(argv=None):
         ap.add_argument(flag, type=typ, default=default, help=text)
     ap.add_argument("--synthetic", action="store_true", help="train on synthetic tiles / RNA rows")
     args = ap.parse_args(argv)
+    from rna_gan_amd.gan_utils import check_flags
+    from rna_gan_amd.metrics import ConditioningFidelity, PrecisionRecall
+    from rna_gan_amd.nearest import FACTORS
+    check_flags(ap, args, binary=("g_ema_warmup", "device_transform", "resident", "mem_d4"), precision=False)   # (--precision: main())
     if not 0.0 <= args.g_ema < 1.0:
         ap.error("--g_ema must be in [0, 1)")
-    if args.g_ema_warmup not in (0, 1):
-        ap.error("--g_ema_warmup must be 0 or 1")
     if args.fd_samples < 0 or args.fd_samples == 1:
         ap.error("--fd_samples must be 0 (off) or at least 2 (a covariance needs two samples)")
     if args.fd_extractor != "discriminator" and not os.path.isfile(args.fd_extractor):
@@ -196,7 +198,7 @@ def parse_args(argv=None):
         ap.error("--div_samples must be 0 (off) or at least 2 (a pair needs two tiles)")
     if args.div_pairs < 0:
         ap.error("--div_pairs must be >= 0")
-    if args.pr_report not in ("precision", "recall", "density", "coverage"):
+    if args.pr_report not in PrecisionRecall.REPORTS:
         ap.error("--pr_report must be precision, recall, density or coverage")
     if args.cf_patients < 0 or args.cf_patients == 1:
         ap.error("--cf_patients must be 0 (off) or at least 2 (a rank among fewer than two patients says nothing)")
@@ -204,24 +206,18 @@ def parse_args(argv=None):
         ap.error("--cf_patients needs --loss_type wganvae (only that generator is conditioned on RNA)")
     if args.cf_tiles < 1:
         ap.error("--cf_tiles must be at least 1")
-    if args.cf_report not in ("top1", "top5", "mrr", "median_rank"):
+    if args.cf_report not in ConditioningFidelity.REPORTS:
         ap.error("--cf_report must be top1, top5, mrr or median_rank")
-    if args.device_transform not in (0, 1):
-        ap.error("--device_transform must be 0 or 1")
     if args.augment not in ("none", "d4"):
         ap.error("--augment must be none or d4")
-    if args.resident not in (0, 1):
-        ap.error("--resident must be 0 or 1")
     if args.resident_max_gb < 0:
         ap.error("--resident_max_gb must be >= 0")
     if args.mem_samples < 0:
         ap.error("--mem_samples must be >= 0")
     if args.mem_samples > 0 and not args.resident:
         ap.error("--mem_samples needs --resident 1: the audit searches the training tiles where they are kept on the device")
-    if args.mem_factor not in (1, 2, 4, 8, 16, 32):
+    if args.mem_factor not in FACTORS:
         ap.error("--mem_factor must be 1, 2, 4, 8, 16 or 32")
-    if args.mem_d4 not in (0, 1):
-        ap.error("--mem_d4 must be 0 or 1")
     return args
 
 
@@ -232,11 +228,8 @@ def metric_inputs(args, n_samples, flag, ds, losses, device, holder):
     the metric's own rows (no collective).  ``holder["trainer"]`` is filled in once the Trainer exists: the noise needs its
     generator.  ``holder`` also keeps what is built here, so two metrics over the same number of samples share one device copy of
     the real set and one noise callable, and all metrics share one extractor."""
-    from rna_gan_amd.fid import inception_features_device
     from rna_gan_amd.representation import latent_prep
-    if "extractor" not in holder:
-        holder["extractor"] = "discriminator" if args.fd_extractor == "discriminator" else \
-            inception_features_device(args.fd_extractor, device)
+    extractor = shared_extractor(args, device, holder)
     shared = holder.setdefault("metric_inputs", {})
     if n_samples in shared:
         return shared[n_samples]
@@ -269,24 +262,39 @@ def metric_inputs(args, n_samples, flag, ds, losses, device, holder):
                 betavae.train(was_training)
                 cache["z"] = latent_prep(u, z)
             return cache["z"]
-    shared[n_samples] = (real, holder["extractor"], noise, min(256, len(items)))
+    shared[n_samples] = (real, extractor, noise, min(256, len(items)))
     return shared[n_samples]
+
+
+def shared_extractor(args, device, holder):
+    """--fd_extractor as the metrics take it, built once and kept in ``holder``: every per-epoch metric uses this one."""
+    if "extractor" not in holder:
+        from rna_gan_amd.fid import inception_features_device
+        holder["extractor"] = "discriminator" if args.fd_extractor == "discriminator" else \
+            inception_features_device(args.fd_extractor, device)
+    return holder["extractor"]
+
+
+def _sampled(args, name, ds, losses, device, holder):
+    """(real, extractor, what every sampling metric's constructor takes) of --<name>_samples: ``metric_inputs`` by flag name"""
+    real, extractor, noise, batch = metric_inputs(args, getattr(args, name + "_samples"), "--%s_samples" % name, ds, losses, device,
+                                                  holder)
+    return real, extractor, dict(noise=noise, seed=args.seed, batch_size=batch)
 
 
 def build_fd_metric(args, ds, losses, device, holder):
     """--fd_samples: the Frechet-distance metric over the first N items of ``ds`` (metric_inputs)."""
     from rna_gan_amd.metrics import FrechetDistance
-    real, extractor, noise, batch = metric_inputs(args, args.fd_samples, "--fd_samples", ds, losses, device, holder)
-    return FrechetDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch)
+    real, extractor, common = _sampled(args, "fd", ds, losses, device, holder)
+    return FrechetDistance(real, extractor=extractor, **common)
 
 
 def build_kid_metric(args, ds, losses, device, holder):
     """--kid_samples: the kernel-distance metric over the first N items of ``ds`` (metric_inputs: with --fd_samples N the same
     device copy of the real set and the same noise callable as the Frechet distance's)."""
     from rna_gan_amd.metrics import KernelDistance
-    real, extractor, noise, batch = metric_inputs(args, args.kid_samples, "--kid_samples", ds, losses, device, holder)
-    return KernelDistance(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch,
-                          num_subsets=args.kid_subsets, subset_size=args.kid_subset_size)
+    real, extractor, common = _sampled(args, "kid", ds, losses, device, holder)
+    return KernelDistance(real, extractor=extractor, num_subsets=args.kid_subsets, subset_size=args.kid_subset_size, **common)
 
 
 def build_qc_metric(args, ds, losses, device, holder):
@@ -294,8 +302,8 @@ def build_qc_metric(args, ds, losses, device, holder):
     (wganvae: built from the RNA rows of the first N items, shared with the other metrics over N samples) and the number of
     readable items, which is the number of generated tiles."""
     from rna_gan_amd.metrics import TissueYield
-    real, _extractor, noise, batch = metric_inputs(args, args.qc_samples, "--qc_samples", ds, losses, device, holder)
-    return TissueYield(int(real.shape[0]), noise=noise, seed=args.seed, batch_size=batch)
+    real, _extractor, common = _sampled(args, "qc", ds, losses, device, holder)
+    return TissueYield(int(real.shape[0]), **common)
 
 
 def build_div_metric(args, ds, losses, device, holder):
@@ -304,9 +312,8 @@ def build_div_metric(args, ds, losses, device, holder):
     ``export.tiles_u8`` -- are the real baseline the same pair list is evaluated over."""
     from rna_gan_amd.export import tiles_u8
     from rna_gan_amd.metrics import PairDiversity
-    real, _extractor, noise, batch = metric_inputs(args, args.div_samples, "--div_samples", ds, losses, device, holder)
-    return PairDiversity(int(real.shape[0]), pairs=args.div_pairs or None, real=tiles_u8(real.float().contiguous()), noise=noise,
-                         seed=args.seed, batch_size=batch)
+    real, _extractor, common = _sampled(args, "div", ds, losses, device, holder)
+    return PairDiversity(int(real.shape[0]), pairs=args.div_pairs or None, real=tiles_u8(real.float().contiguous()), **common)
 
 
 def build_mem_metric(args, ds, losses, device, holder):
@@ -314,21 +321,19 @@ def build_mem_metric(args, ds, losses, device, holder):
     yet; main() hands it over with ``set_train`` -- and with metric_inputs' noise, as the tissue yield (wganvae: from the RNA rows of
     the first N items, shared with the other metrics over N samples)."""
     from rna_gan_amd.metrics import Memorisation
-    real, _extractor, noise, batch = metric_inputs(args, args.mem_samples, "--mem_samples", ds, losses, device, holder)
-    return Memorisation(None, int(real.shape[0]), factor=args.mem_factor, d4=bool(args.mem_d4), noise=noise, seed=args.seed,
-                        batch_size=batch)
+    real, _extractor, common = _sampled(args, "mem", ds, losses, device, holder)
+    return Memorisation(None, int(real.shape[0]), factor=args.mem_factor, d4=bool(args.mem_d4), **common)
 
 
 def build_pr_metric(args, ds, losses, device, holder):
     """--pr_samples: precision / recall / density / coverage over the first N items of ``ds`` (metric_inputs: with --fd_samples N
     or --kid_samples N the same device copy of the real set, the same noise callable and the same extractor)."""
     from rna_gan_amd.metrics import PrecisionRecall
-    real, extractor, noise, batch = metric_inputs(args, args.pr_samples, "--pr_samples", ds, losses, device, holder)
+    real, extractor, common = _sampled(args, "pr", ds, losses, device, holder)
     if real.shape[0] < args.pr_k + 1:
         raise SystemExit("--pr_samples: %d readable tiles among the first %d items, --pr_k %d needs %d"
                          % (real.shape[0], args.pr_samples, args.pr_k, args.pr_k + 1))
-    return PrecisionRecall(real, extractor=extractor, noise=noise, seed=args.seed, batch_size=batch, nearest_k=args.pr_k,
-                           report=args.pr_report)
+    return PrecisionRecall(real, extractor=extractor, nearest_k=args.pr_k, report=args.pr_report, **common)
 
 
 def build_cf_metric(args, ds, losses, device, holder):
@@ -336,10 +341,6 @@ def build_cf_metric(args, ds, losses, device, holder):
     row, the rule of DeviceTileSet.from_dataset -- each with its first --cf_tiles readable tiles (held on the device; uint8 under
     --device_transform / --resident, normalised on the device as the training batches are).  The extractor is the shared one."""
     from rna_gan_amd.metrics import ConditioningFidelity
-    if "extractor" not in holder:
-        from rna_gan_amd.fid import inception_features_device
-        holder["extractor"] = "discriminator" if args.fd_extractor == "discriminator" else \
-            inception_features_device(args.fd_extractor, device)
     P_, T = args.cf_patients, args.cf_tiles
     rows, row_index, tiles, patient_of, have = [], {}, [], [], []
     known = getattr(ds, "rna_data_arrays", None)           # a PatchRNADataset: the rows without decoding a tile
@@ -371,8 +372,14 @@ def build_cf_metric(args, ds, losses, device, holder):
         raise SystemExit("--cf_patients: %d distinct RNA rows among %d items, %d of them without a readable tile"
                          % (len(rows), len(ds), sum(1 for h in have if h < 1)))
     return ConditioningFidelity(torch.stack(tiles).to(device), torch.tensor(patient_of, dtype=torch.int32), torch.stack(rows),
-                                losses[0].betavae, tiles_per_patient=T, extractor=holder["extractor"], seed=args.seed,
-                                batch_size=256, report=args.cf_report)
+                                losses[0].betavae, tiles_per_patient=T, extractor=shared_extractor(args, device, holder),
+                                seed=args.seed, batch_size=256, report=args.cf_report)
+
+
+# (what switches it on, what builds it): the per-epoch metrics in the order they are evaluated and logged
+METRIC_BUILDERS = (("fd_samples", build_fd_metric), ("kid_samples", build_kid_metric), ("pr_samples", build_pr_metric),
+                   ("qc_samples", build_qc_metric), ("div_samples", build_div_metric), ("cf_patients", build_cf_metric),
+                   ("mem_samples", build_mem_metric))
 
 
 def main():
@@ -413,19 +420,12 @@ def main():
         # rna_ columns] -> per-slide tile sampling from the slide databases -> batches; rna_gan_amd.data restates the
         # record format / sampling / preparation (LMDB files need the `lmdb` package, directory stores do not)
         from rna_gan_amd import data as PD
-        import random
+        from rna_gan_amd.gan_utils import training_dataset
         # every rank must build the SAME tile list (the datasets draw their per-slide tile sample from the global `random`
-        # generator, src/read_data.py:313-316), so that the strided shards below partition one list
-        random.seed(args.seed)
-        patch_data_path = config["patch_data_path"]
-        train_df = PD.load_slide_tables(config["path_csv"], patch_data_path)
-        # None: uint8 tiles, normalised on the device
-        tf = None if args.device_transform or args.resident else PD.ToFloatNormalize(0.5, 0.5)
-        if with_rna:
-            train_df, _, _ = PD.log_standardize_rna(train_df)
-            ds = PD.PatchRNADataset(patch_data_path, train_df, img_size, max_patches_total=args.num_patches, transforms=tf)
-        else:
-            ds = PD.PatchDataset(patch_data_path, train_df, img_size, max_patches_total=args.num_patches, transforms=tf)
+        # generator, src/read_data.py:313-316, seeded here), so that the strided shards below partition one list
+        # transforms None: uint8 tiles, normalised on the device
+        ds = training_dataset(config, args.seed, args.num_patches, with_rna,
+                              None if args.device_transform or args.resident else PD.ToFloatNormalize(0.5, 0.5))
 
         world = D_.world_size()
         collate_fn = make_collate_fn(with_rna, world)
@@ -471,23 +471,9 @@ def main():
     epochs = args.num_epochs if args.num_epochs is not None else 5
     print("Device: {}".format(device)); print("Epochs: {}".format(epochs))
     holder = {"input_transform": input_transform}
-    metrics = []
-    if D_.rank() == 0:                                    # the per-epoch metrics are evaluated by rank 0 alone
-        if args.fd_samples > 0:
-            metrics.append(build_fd_metric(args, ds, losses, device, holder))
-        if args.kid_samples > 0:
-            metrics.append(build_kid_metric(args, ds, losses, device, holder))
-        if args.pr_samples > 0:
-            metrics.append(build_pr_metric(args, ds, losses, device, holder))
-        if args.qc_samples > 0:
-            metrics.append(build_qc_metric(args, ds, losses, device, holder))
-        if args.div_samples > 0:
-            metrics.append(build_div_metric(args, ds, losses, device, holder))
-        if args.cf_patients > 0:
-            metrics.append(build_cf_metric(args, ds, losses, device, holder))
-        if args.mem_samples > 0:
-            metrics.append(build_mem_metric(args, ds, losses, device, holder))
-    metrics = metrics or None
+    built = {flag: build(args, ds, losses, device, holder)  # the per-epoch metrics are evaluated by rank 0 alone
+             for flag, build in METRIC_BUILDERS if D_.rank() == 0 and getattr(args, flag) > 0}
+    metrics = list(built.values()) or None
     trainer = P.Trainer(gan_network, losses, metrics_list=metrics, checkpoints=args.model_dir, sample_size=64, epochs=epochs, devices=[0],
                         recon=args.image_dir, device=device, precision=args.precision, loss_scaling=args.loss_scaling,
                         ema_decay=args.g_ema if args.g_ema > 0.0 else None, ema_warmup=bool(args.g_ema_warmup),
@@ -504,9 +490,8 @@ def main():
         loader = DeviceTileLoader(tiles, args.batch_size, transform=input_transform, seed=args.seed, rank=D_.rank())
         if len(loader) == 0:
             raise SystemExit("--resident 1: %d readable tiles do not fill one batch of %d" % (len(tiles), args.batch_size))
-        for metric in metrics or []:
-            if hasattr(metric, "set_train"):              # --mem_samples: the audit searches the rank's resident tiles
-                metric.set_train(tiles)
+        if "mem_samples" in built:                        # the audit searches the rank's resident tiles
+            built["mem_samples"].set_train(tiles)
     if args.checkpoint is not None:
         trainer.load_model(load_path=args.checkpoint)
     for loss in losses:                                   # identical frozen encoders on every rank (rank 0's)

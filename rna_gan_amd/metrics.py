@@ -44,20 +44,98 @@ def _eval_mode(*modules):
             m.train(was)
 
 
-def _feature_extractor(extractor, discriminator):
-    """``(extract, resize)`` of a metric's ``extractor`` setting: the discriminator trunk at native resolution (no resize), or
-    the callable behind a resize to 299 x 299"""
+def feature_extractor(extractor, discriminator, device=None):
+    """``(extract, resize)`` of an ``extractor`` setting: "discriminator" -- the discriminator trunk at native resolution (no
+    resize); a callable, or the path of a torchvision inception_v3 state dict (loaded onto ``device``) -- behind a resize to
+    299 x 299"""
+    from . import fid
     if extractor == "discriminator":
-        from .fid import discriminator_features_device
-        return discriminator_features_device(discriminator), None
+        return fid.discriminator_features_device(discriminator), None
+    if isinstance(extractor, str):
+        extractor = fid.inception_features_device(extractor, device)
     return extractor, 299
 
 
+def _checked_extractor(extractor):
+    if not (extractor == "discriminator" or callable(extractor)):
+        raise ValueError("extractor must be 'discriminator' or a callable device-side feature extractor")
+    return extractor
+
+
+def _checked_tiles(tiles, name, rows, least):
+    """``tiles`` if it is a (rows >= least, 3, S, S) tensor of uint8 or float tiles"""
+    if not torch.is_tensor(tiles) or tiles.dim() != 4 or tiles.shape[1] != 3 or tiles.shape[0] < least:
+        raise ValueError("%s must be an (%s, 3, S, S) tensor of tiles" % (name, rows))
+    if tiles.dtype != torch.uint8 and not tiles.is_floating_point():
+        raise TypeError("%s must be uint8 or float tiles" % name)
+    return tiles
+
+
 class EvaluationMetric:
-    """torchgan.metrics.EvaluationMetric (recalled): base class of everything in ``metrics_list``."""
+    """torchgan.metrics.EvaluationMetric (recalled): base class of everything in ``metrics_list``.
+
+    What a metric pickles (the trainer pickles its metrics into every checkpoint) is declared, not written out: a class names
+    its ``SETTINGS`` (attributes pickled as they are), what is ``DROPPED`` (data, caches and results: never pickled, None
+    after unpickling) and whether it keeps a ``HISTORY`` (``self.history``, one dictionary per evaluation, pickled); the
+    declarations of all classes along the MRO add up.  A class that declares no settings pickles as any object does."""
+
+    SETTINGS, DROPPED, HISTORY = (), (), False
+    PRIVATE_NOISE = False          # draws from ``self._rng``, a private torch.Generator(self.seed) that is never pickled
 
     def __init__(self):
         self.arg_map = {}
+
+    @classmethod
+    def _declared(cls, what):
+        return [name for c in reversed(cls.__mro__) for name in vars(c).get(what, ())]
+
+    def __getstate__(self):
+        settings = self._declared("SETTINGS")
+        state = {name: getattr(self, name) for name in settings} if settings else dict(self.__dict__)
+        state["arg_map"] = dict(self.arg_map)
+        if "extractor" in state and not isinstance(state["extractor"], str):
+            state["extractor"] = "callable"
+        if self.HISTORY:
+            state["history"] = [dict(h) for h in self.history]
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        for name in self._declared("DROPPED"):
+            setattr(self, name, None)
+        if self.HISTORY:
+            self.history = [dict(h) for h in state.get("history", [])]
+        if self.PRIVATE_NOISE:
+            self._rng = torch.Generator().manual_seed(self.seed)
+
+    def adopt_history(self, saved):
+        """Go on from the history of ``saved``, this metric as a checkpoint holds it (or None): a copy, dictionary by
+        dictionary; the live object keeps everything else."""
+        old = getattr(saved, "history", None)
+        if isinstance(old, list) and hasattr(self, "history"):
+            self.history = [dict(h) for h in old]
+
+    def _record(self, scores, report):
+        """One evaluation: ``scores`` kept in ``last`` and, where the class keeps a history, appended to it as a copy; the
+        float the trainer logs"""
+        self.last = scores
+        if self.HISTORY:
+            self.history.append(dict(scores))
+        return float(scores[report])
+
+    def _require(self, data, what, setter):
+        if data is None:
+            raise RuntimeError("%s: no %s (an unpickled metric keeps its settings only: call %s)" % (type(self).__name__, what, setter))
+
+    def _real_side(self, attr, compute, fixed):
+        """The real set's part of an evaluation, cached in ``attr``: as kept, or ``compute()`` -- which is kept only when
+        ``fixed`` (a fixed extractor: it never changes)"""
+        value = getattr(self, attr)
+        if value is None:
+            value = compute()
+            if fixed:
+                setattr(self, attr, value)
+        return value
 
     def set_arg_map(self, value):
         """Rename arguments of ``metric_ops``: {argument name: trainer attribute name}."""
@@ -78,7 +156,11 @@ class _GeneratedSamples(EvaluationMetric):
     None ((n_fake, E) standard normal values drawn ONCE from a private torch.Generator(seed): at construction when
     ``encoding_dims`` is given, else at the first evaluation from the generator's ``encoding_dims`` -- the same values either
     way), a tensor of n_fake rows, or a callable noise(n) called at every evaluation.  ``count`` names n_fake in the messages
-    of the constructor; ``least`` is its smallest value."""
+    of the constructor; ``least`` is its smallest value.  ``preprocess`` turns generated images into the uint8 tiles a store
+    would hold, in ``LAYOUT``."""
+
+    SETTINGS, DROPPED, PRIVATE_NOISE = ("n_fake", "seed", "batch_size"), ("noise",), True
+    LAYOUT = "nhwc"
 
     def __init__(self, n_fake, noise, seed, batch_size, encoding_dims, count="n_fake", least=1):
         super().__init__()
@@ -96,10 +178,11 @@ class _GeneratedSamples(EvaluationMetric):
         if noise is None and encoding_dims is not None:
             self.noise = torch.randn(self.n_fake, int(encoding_dims), generator=self._rng)
 
-    def __setstate__(self, state):
-        self.__dict__.update(state)
-        self.noise = None
-        self._rng = torch.Generator().manual_seed(self.seed)
+    def preprocess(self, x):
+        """fp32 [-1, 1] NCHW images -> the uint8 tiles a store would hold (the rounding rule), on the device: interleaved RGB,
+        or planar -- the training set's layout -- under ``LAYOUT = "nchw"``."""
+        from .export import tiles_u8
+        return tiles_u8(x.float().contiguous(), layout=self.LAYOUT)
 
     def _noise_for(self, generator, device):
         if callable(self.noise):
@@ -135,10 +218,10 @@ class _GeneratedAgainstReal(_GeneratedSamples):
     evaluation frame (eval mode under no_grad, modes restored, the real set's result cached for a fixed extractor).  A subclass
     supplies ``metric_ops`` and what is collected from a set's batches."""
 
+    SETTINGS, DROPPED = ("extractor",), ("real", "_real_stats")
+
     def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None):
-        if not (extractor == "discriminator" or callable(extractor)):
-            raise ValueError("extractor must be 'discriminator' or a callable device-side feature extractor")
-        self.extractor = extractor
+        self.extractor = _checked_extractor(extractor)
         self._real_stats = None
         self.real = None
         self.set_real(real)
@@ -146,20 +229,7 @@ class _GeneratedAgainstReal(_GeneratedSamples):
 
     # ------------------------------------------------------------------ data
     def set_real(self, real):
-        if not torch.is_tensor(real) or real.dim() != 4 or real.shape[1] != 3 or real.shape[0] < 2:
-            raise ValueError("real must be an (N >= 2, 3, S, S) tensor of tiles")
-        if real.dtype != torch.uint8 and not real.is_floating_point():
-            raise TypeError("real must be uint8 or float tiles")
-        self.real = real
-        self._real_stats = None
-
-    def __getstate__(self):
-        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
-                "extractor": self.extractor if isinstance(self.extractor, str) else "callable"}
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        self.real = None
+        self.real = _checked_tiles(real, "real", "N >= 2", 2)
         self._real_stats = None
 
     # ------------------------------------------------------------------ torchgan's hooks
@@ -178,18 +248,12 @@ class _GeneratedAgainstReal(_GeneratedSamples):
     def _collect_sets(self, generator, discriminator, device, collect):
         """(fake, real): ``collect(batches, extract, resize)`` of the generated set and of the real set (the latter kept in
         ``_real_stats`` for a fixed extractor), both networks in eval mode, their modes restored"""
-        if self.real is None:
-            raise RuntimeError("%s: no real set (an unpickled metric keeps its settings only: call set_real)" % type(self).__name__)
+        self._require(self.real, "real set", "set_real")
         with _eval_mode(generator, discriminator):
-            extract, resize = _feature_extractor(self.extractor, discriminator)
+            extract, resize = feature_extractor(self.extractor, discriminator)
             z = self._noise_for(generator, device)
             fake = collect(self._fake_batches(generator, z), extract, resize)
-            real = self._real_stats
-            if real is None:
-                real = collect(self._real_batches(device), extract, resize)
-                if resize is not None:                       # a fixed extractor: the real set's result never changes
-                    self._real_stats = real
-            return fake, real
+            return fake, self._real_side("_real_stats", lambda: collect(self._real_batches(device), extract, resize), resize is not None)
 
 
 class FrechetDistance(_GeneratedAgainstReal):
@@ -238,6 +302,8 @@ class KernelDistance(_GeneratedAgainstReal):
     two sets follow one distribution, and it can be slightly negative (the estimator is unbiased).  The whole dictionary of
     kid.kernel_distance is kept in ``self.last``."""
 
+    SETTINGS, DROPPED = ("num_subsets", "subset_size", "degree", "gamma", "coef0"), ("last",)
+
     def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None,
                  num_subsets=0, subset_size=1000, degree=3, gamma=None, coef0=1.0):
         super().__init__(real, n_fake, extractor, noise, seed, batch_size, encoding_dims)
@@ -253,16 +319,6 @@ class KernelDistance(_GeneratedAgainstReal):
             raise ValueError("gamma must be > 0 (or None for 1 / F)")
         self.last = None
 
-    def __getstate__(self):
-        state = super().__getstate__()
-        state.update(num_subsets=self.num_subsets, subset_size=self.subset_size, degree=self.degree, gamma=self.gamma,
-                     coef0=self.coef0)
-        return state
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        self.last = None
-
     def calculate_score(self, fake_feats, real_feats=None):
         from .kid import kernel_distance
         return kernel_distance(fake_feats, real_feats, num_subsets=self.num_subsets, subset_size=self.subset_size, seed=self.seed,
@@ -272,8 +328,7 @@ class KernelDistance(_GeneratedAgainstReal):
         from . import fid as FID
         fake, real = self._collect_sets(generator, discriminator, device, lambda batches, extract, resize: FID.device_features(
             batches, extract, resize=resize, value_range=(-1, 1)))
-        self.last = self.calculate_score(fake, real)
-        return float(self.last["subset_mean"] if self.num_subsets > 0 else self.last["mmd2"])
+        return self._record(self.calculate_score(fake, real), "subset_mean" if self.num_subsets > 0 else "mmd2")
 
 
 class PrecisionRecall(_GeneratedAgainstReal):
@@ -293,6 +348,7 @@ class PrecisionRecall(_GeneratedAgainstReal):
     are computed once and cached."""
 
     REPORTS = ("precision", "recall", "density", "coverage")
+    SETTINGS, DROPPED, HISTORY = ("nearest_k", "report"), ("last", "_real_radii"), True
 
     def __init__(self, real, n_fake=None, extractor="discriminator", noise=None, seed=0, batch_size=256, encoding_dims=None,
                  nearest_k=5, report="recall"):
@@ -314,17 +370,6 @@ class PrecisionRecall(_GeneratedAgainstReal):
             raise ValueError("real has %d tiles: nearest_k = %d needs at least %d" % (self.real.shape[0], self.nearest_k, self.nearest_k + 1))
         self._real_radii = None
 
-    def __getstate__(self):
-        state = super().__getstate__()
-        state.update(nearest_k=self.nearest_k, report=self.report, history=[dict(h) for h in self.history])
-        return state
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        self.last = None
-        self._real_radii = None
-        self.history = [dict(h) for h in state.get("history", [])]
-
     def calculate_score(self, fake_feats, real_feats=None, real_radii2=None):
         from .prdc import prdc
         return prdc(real_feats, fake_feats, k=self.nearest_k, real_radii2=real_radii2)
@@ -334,14 +379,9 @@ class PrecisionRecall(_GeneratedAgainstReal):
         from .prdc import knn_radii2
         fake, real = self._collect_sets(generator, discriminator, device, lambda batches, extract, resize: FID.device_features(
             batches, extract, resize=resize, value_range=(-1, 1)))
-        radii = self._real_radii
-        if radii is None:
-            radii = knn_radii2(real, self.nearest_k)
-            if self._real_stats is not None:                 # a fixed extractor: the real features are cached, so are their radii
-                self._real_radii = radii
-        self.last = self.calculate_score(fake, real, radii)
-        self.history.append(dict(self.last))
-        return float(self.last[self.report])
+        # a fixed extractor: the real features are cached, so are their radii
+        radii = self._real_side("_real_radii", lambda: knn_radii2(real, self.nearest_k), self._real_stats is not None)
+        return self._record(self.calculate_score(fake, real, radii), self.report)
 
 
 class TissueYield(_GeneratedSamples):
@@ -359,6 +399,9 @@ class TissueYield(_GeneratedSamples):
     {"accepted", "tissue_fraction" (the mean over the tiles), "low_contrast" (the fraction of low-contrast tiles)}; the
     TileStats of the last evaluation is ``self.last_stats``.  Pickling keeps the settings and ``history``, never the noise."""
 
+    SETTINGS = ("min_tissue", "fraction", "luma_range", "rgb_min", "dilate", "percentiles")
+    DROPPED, HISTORY = ("last", "last_stats"), True
+
     def __init__(self, samples, min_tissue=0.2, rgb_min=50, dilate=3, percentiles=(1, 99), fraction=0.05, luma_range=2.0,
                  noise=None, seed=0, batch_size=256, encoding_dims=None):
         super().__init__(samples, noise, seed, batch_size, encoding_dims, count="samples")
@@ -369,21 +412,6 @@ class TissueYield(_GeneratedSamples):
             raise ValueError("rgb_min must be in 0..255 and dilate in 0..%d" % MAX_DILATE)
         percentile_ranks(2, self.percentiles)                    # two percentiles in [0, 100]
         self.last, self.last_stats, self.history = None, None, []
-
-    def __getstate__(self):
-        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
-                "min_tissue": self.min_tissue, "fraction": self.fraction, "luma_range": self.luma_range, "rgb_min": self.rgb_min,
-                "dilate": self.dilate, "percentiles": self.percentiles, "history": [dict(h) for h in self.history]}
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        self.last, self.last_stats = None, None
-        self.history = [dict(h) for h in state.get("history", [])]
-
-    def preprocess(self, x):
-        """fp32 [-1, 1] NCHW images -> the uint8 tiles a store would hold (interleaved RGB, the rounding rule), on the device."""
-        from .export import tiles_u8
-        return tiles_u8(x.float().contiguous())
 
     def calculate_score(self, stats):
         from . import tissue as TQ
@@ -402,9 +430,7 @@ class TissueYield(_GeneratedSamples):
         stats = TQ.stats_from_rows(torch.cat(rows).cpu().numpy() if rows else np.zeros((0, 12), np.int32), H, W, self.rgb_min,
                                    self.dilate, self.percentiles)                       # ONE download: 48 bytes per tile
         self.last_stats = stats
-        self.last = self.calculate_score(stats)
-        self.history.append(dict(self.last))
-        return float(self.last["accepted"])
+        return self._record(self.calculate_score(stats), "accepted")
 
 
 class ConditioningFidelity(EvaluationMetric):
@@ -432,15 +458,16 @@ class ConditioningFidelity(EvaluationMetric):
     one without it.  Pickling keeps the settings and ``history`` only; ``set_data`` re-supplies tiles, ids, rows and encoder."""
 
     REPORTS = ("top1", "top5", "mrr", "median_rank")
+    SETTINGS = ("tiles_per_patient", "seed", "batch_size", "group", "center", "report", "extractor")
+    DROPPED, HISTORY = ("real_tiles", "patient_of", "rna", "betavae", "_real_centroids", "last", "last_rank"), True
 
     def __init__(self, real_tiles, patient_of, rna, betavae, tiles_per_patient=8, extractor="discriminator", seed=0,
                  batch_size=256, center=True, report="top1", group=4096):
         super().__init__()
-        if not (extractor == "discriminator" or callable(extractor)):
-            raise ValueError("extractor must be 'discriminator' or a callable device-side feature extractor")
+        self.extractor = _checked_extractor(extractor)
         if report not in self.REPORTS:
             raise ValueError("report must be one of %s" % ", ".join(self.REPORTS))
-        self.extractor, self.report, self.center = extractor, report, bool(center)
+        self.report, self.center = report, bool(center)
         self.tiles_per_patient, self.seed, self.batch_size, self.group = int(tiles_per_patient), int(seed), int(batch_size), int(group)
         if self.tiles_per_patient < 1 or self.batch_size < 1 or self.group < 2:
             raise ValueError("tiles_per_patient and batch_size must be >= 1 and group >= 2")
@@ -454,10 +481,7 @@ class ConditioningFidelity(EvaluationMetric):
         return cls(ts.tiles, ts.row_of, ts.rna, betavae, **kwargs)
 
     def set_data(self, real_tiles, patient_of, rna, betavae):
-        if not torch.is_tensor(real_tiles) or real_tiles.dim() != 4 or real_tiles.shape[1] != 3:
-            raise ValueError("real_tiles must be an (M, 3, S, S) tensor of tiles")
-        if real_tiles.dtype != torch.uint8 and not real_tiles.is_floating_point():
-            raise TypeError("real_tiles must be uint8 or float tiles")
+        _checked_tiles(real_tiles, "real_tiles", "M", 0)
         if not torch.is_tensor(rna) or rna.dim() != 2 or rna.shape[0] < 2:
             raise ValueError("rna must be (P >= 2, features): a rank among fewer than two patients says nothing")
         patient_of = torch.as_tensor(patient_of)
@@ -472,19 +496,6 @@ class ConditioningFidelity(EvaluationMetric):
         self.real_tiles, self.patient_of, self.rna, self.betavae = real_tiles, patient_of.to(torch.int32), rna, betavae
         self._real_centroids = None
 
-    def __getstate__(self):
-        return {"arg_map": dict(self.arg_map), "tiles_per_patient": self.tiles_per_patient, "seed": self.seed,
-                "batch_size": self.batch_size, "group": self.group, "center": self.center, "report": self.report,
-                "extractor": self.extractor if isinstance(self.extractor, str) else "callable",
-                "history": [dict(h) for h in self.history]}
-
-    def __setstate__(self, state):
-        self.__dict__.update(state)
-        self.real_tiles = self.patient_of = self.rna = self.betavae = None
-        self._real_centroids = None
-        self.last, self.last_rank = None, None
-        self.history = [dict(h) for h in state.get("history", [])]
-
     def calculate_score(self, fake_centroids, real_centroids=None):
         from .representation import match_ranks, retrieval_scores
         rank, _ = match_ranks(fake_centroids, real_centroids, None, self.center)
@@ -493,23 +504,17 @@ class ConditioningFidelity(EvaluationMetric):
 
     @torch.no_grad()
     def metric_ops(self, generator, discriminator, device):
-        if self.real_tiles is None:
-            raise RuntimeError("ConditioningFidelity: no data (an unpickled metric keeps its settings only: call set_data)")
+        self._require(self.real_tiles, "data", "set_data")
         from .representation import patient_representations
         with _eval_mode(generator, discriminator):
-            extract, resize = _feature_extractor(self.extractor, discriminator)
-            real = self._real_centroids
-            reps = patient_representations(extract, real=(self.real_tiles, self.patient_of) if real is None else None,
+            extract, resize = feature_extractor(self.extractor, discriminator)
+            have = self._real_centroids is not None
+            reps = patient_representations(extract, real=None if have else (self.real_tiles, self.patient_of),
                                            conditioned=generator, betavae=self.betavae, gene_exp=self.rna,
                                            tiles_per_patient=self.tiles_per_patient, n_patients=self.rna.shape[0], seed=self.seed,
                                            batch_size=self.batch_size, group=self.group, resize=resize)
-            if real is None:
-                real = reps["real"]
-                if resize is not None:                       # a fixed extractor: the real centroids never change
-                    self._real_centroids = real
-            self.last = self.calculate_score(reps["conditioned"], real)
-            self.history.append(dict(self.last))
-            return float(self.last[self.report])
+            real = self._real_side("_real_centroids", lambda: reps["real"], resize is not None)
+            return self._record(self.calculate_score(reps["conditioned"], real), self.report)
 
 
 class Memorisation(_GeneratedSamples):
@@ -534,6 +539,9 @@ class Memorisation(_GeneratedSamples):
     ConditioningFidelity.from_tile_set does; there is no index across ranks, so a copy of another rank's tile is not seen.
     Pickling keeps the settings and ``history``; tiles, index and noise are never pickled (``set_train`` re-supplies the tiles)."""
 
+    SETTINGS, DROPPED, HISTORY = ("factor", "k", "d4"), ("train_tiles", "heldout", "_index", "last", "last_result"), True
+    LAYOUT = "nchw"                # planar uint8 tiles: the training set's layout
+
     def __init__(self, train_tiles, samples, factor=4, k=1, d4=False, heldout=None, noise=None, seed=0, batch_size=256,
                  encoding_dims=None):
         super().__init__(samples, noise, seed, batch_size, encoding_dims, count="samples")
@@ -556,21 +564,6 @@ class Memorisation(_GeneratedSamples):
                 raise ValueError("training and held-out tiles are (M, C, S, S) uint8 tensors")
         self.train_tiles, self.heldout, self._index = train_tiles, heldout, None
 
-    def __getstate__(self):
-        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
-                "factor": self.factor, "k": self.k, "d4": self.d4, "history": [dict(h) for h in self.history]}
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        self.train_tiles = self.heldout = self._index = None
-        self.last, self.last_result = None, None
-        self.history = [dict(h) for h in state.get("history", [])]
-
-    def preprocess(self, x):
-        """fp32 [-1, 1] NCHW images -> planar uint8 tiles (the bytes a store would hold, the training set's layout), on the device."""
-        from .export import tiles_u8
-        return tiles_u8(x.float().contiguous(), layout="nchw")
-
     def calculate_score(self, generated_u8):
         from .nearest import TrainIndex, audit
         if self._index is None:
@@ -580,11 +573,8 @@ class Memorisation(_GeneratedSamples):
         return self.last_result.summary()
 
     def metric_ops(self, generator, device):
-        if self.train_tiles is None:
-            raise RuntimeError("Memorisation: no training tiles (an unpickled metric keeps its settings only: call set_train)")
-        self.last = self.calculate_score(torch.cat(self.generated_tiles(generator, device)))
-        self.history.append(dict(self.last))
-        return float(self.last["copy_rate"])
+        self._require(self.train_tiles, "training tiles", "set_train")
+        return self._record(self.calculate_score(torch.cat(self.generated_tiles(generator, device))), "copy_rate")
 
 
 class PairDiversity(_GeneratedSamples):
@@ -605,6 +595,8 @@ class PairDiversity(_GeneratedSamples):
     ``self.history`` keep {"generated", "real", "gap" (generated - real; both None without real tiles), "per_scale" ([S][2]: the means
     of CS_s and SSIM_s over the generated pairs)}; the per-pair scores of the last evaluation are ``self.last_scores``.
     Pickling keeps the settings and ``history``, never the noise or the tiles (``set_real`` re-supplies the real tiles)."""
+
+    SETTINGS, DROPPED, HISTORY = ("pairs", "scales"), ("real", "_real_score", "last", "last_scores"), True
 
     def __init__(self, samples, pairs=None, real=None, scales=None, noise=None, seed=0, batch_size=256, encoding_dims=None):
         super().__init__(samples, noise, seed, batch_size, encoding_dims, count="samples", least=2)
@@ -627,24 +619,9 @@ class PairDiversity(_GeneratedSamples):
                 raise ValueError("real holds %d tiles, the pair list runs over %d" % (tiles.shape[0], self.n_fake))
         self.real, self._real_score = tiles, None
 
-    def __getstate__(self):
-        return {"arg_map": dict(self.arg_map), "n_fake": self.n_fake, "seed": self.seed, "batch_size": self.batch_size,
-                "pairs": self.pairs, "scales": self.scales, "history": [dict(h) for h in self.history]}
-
-    def __setstate__(self, state):
-        super().__setstate__(state)
-        self.real = self._real_score = None
-        self.last, self.last_scores = None, None
-        self.history = [dict(h) for h in state.get("history", [])]
-
     def pair_list(self):
         from .msssim import random_pairs
         return random_pairs(self.n_fake, self.pairs, self.seed)
-
-    def preprocess(self, x):
-        """fp32 [-1, 1] NCHW images -> the uint8 tiles a store would hold (interleaved RGB, the rounding rule), on the device."""
-        from .export import tiles_u8
-        return tiles_u8(x.float().contiguous())
 
     def calculate_score(self, tiles, layout="nhwc"):
         """(the per-pair MS-SSIM, the diversity dictionary) of the metric's pair list over a tile set"""
@@ -655,11 +632,11 @@ class PairDiversity(_GeneratedSamples):
     def metric_ops(self, generator, device):
         tiles = torch.cat(self.generated_tiles(generator, device))
         self.last_scores, gen = self.calculate_score(tiles)
-        if self.real is not None and self._real_score is None:
+        def real_mean():
+            if self.real is None:
+                return None
             real = self.real.to(device)
-            self._real_score = self.calculate_score(real, "nchw" if real.shape[1] == 3 else "nhwc")[1]["mean"]
-        real = self._real_score
-        self.last = {"generated": gen["mean"], "real": real, "gap": None if real is None else gen["mean"] - real,
-                     "per_scale": gen["per_scale"]}
-        self.history.append(dict(self.last))
-        return float(gen["mean"])
+            return self.calculate_score(real, "nchw" if real.shape[1] == 3 else "nhwc")[1]["mean"]
+        real = self._real_side("_real_score", real_mean, True)       # pixel space: the real tiles' score never changes
+        return self._record({"generated": gen["mean"], "real": real, "gap": None if real is None else gen["mean"] - real,
+                             "per_scale": gen["per_scale"]}, "generated")

@@ -69,6 +69,33 @@ def synthetic_rna(n: int, features: int, seed: int, distinct: int = 16) -> torch
     return torch.from_numpy(rows[idx])
 
 
+def evaluation_inputs(config, sample_size: int, seed: int, device, tissues: bool = False, second_generator: bool = False):
+    """What the evaluation CLIs run on under ``--synthetic``: (tile set, generator, discriminator, betaVAE, second generator
+    or None), all seeded and on ``device``, of the shapes in ``config`` -- ``synthetic_patients`` (default 8) expression rows of
+    ``rna_features`` values, each with ``sample_size`` tiles of ``img_size``; networks of ``encoding_dims`` (64) and
+    ``step_channels`` (4).  Seeds: tiles ``seed``, rows + 1, generator + 2, discriminator + 3, betaVAE + 4.
+    tissues: the rows carry two alternating tissue labels.  second_generator: an unconditioned generator at ``seed + 5``."""
+    from .betavae import betaVAE
+    from .models import DCGANDiscriminator, DCGANGenerator
+    from .resident import DeviceTileSet
+    size, features = int(config["img_size"]), int(config.get("rna_features", 19198))
+    patients, enc = int(config.get("synthetic_patients", 8)), int(config.get("encoding_dims", 64))
+    step = int(config.get("step_channels", 4))
+    n = patients * sample_size
+    row_of = torch.arange(n, dtype=torch.int32) % patients
+    ts = DeviceTileSet.from_tensors(synthetic_tiles_u8(n, size, seed), rna=synthetic_rna(patients, features, seed + 1, distinct=patients),
+                                    row_of=row_of, labels=(row_of % 2).float() if tissues else None, device=device)
+
+    def generator(seed):
+        g = DCGANGenerator(enc, size, 3, step, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.Tanh())
+        return seeded_fill_(g, seed).to(device)
+    G = generator(seed + 2)
+    D = seeded_fill_(DCGANDiscriminator(size, 3, step, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.LeakyReLU(0.2)),
+                     seed + 3).to(device)
+    bv = seeded_fill_(betaVAE(features, enc, [40, 36, enc], [36, 40], beta=0.0005), seed + 4).to(device)
+    return ts, G, D, bv, (generator(seed + 5) if second_generator else None)
+
+
 def synthetic_uniform(n: int, dims: int, seed: int, lo=-0.3, hi=0.3) -> torch.Tensor:
     """The uniform draw of a train_op (src/wgan_loss.py:100), seeded: same values as the oracle's generator."""
     rng = np.random.default_rng(seed)

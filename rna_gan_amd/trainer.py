@@ -198,9 +198,8 @@ class Trainer:
                 self.metric_logs.setdefault(name, [])
             saved_metrics = checkpoint.get("metric_objects")
             for name, metric in self.metrics.items():      # a metric that keeps a per-epoch history (PrecisionRecall) goes on
-                old = getattr(saved_metrics.get(name), "history", None) if isinstance(saved_metrics, dict) else None
-                if isinstance(old, list) and hasattr(metric, "history"):     # from the checkpoint's; the live object is kept
-                    metric.history = [dict(h) for h in old]
+                if isinstance(saved_metrics, dict):         # from the checkpoint's; the live object is kept
+                    metric.adopt_history(saved_metrics.get(name))
             for load_item in self.model_names + self.optimizer_names:
                 getattr(self, load_item).load_state_dict(checkpoint[load_item])
             if self.loss_scaler is not None and "loss_scaler" in checkpoint:

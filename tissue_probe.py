@@ -28,9 +28,6 @@ import os
 
 import numpy as np
 import torch
-import torch.nn as nn
-
-import rna_gan_amd as P
 
 
 def parse_args(argv=None):
@@ -62,37 +59,10 @@ def parse_args(argv=None):
     return args
 
 
-def _synthetic_inputs(args, config, device):
-    """(tile set with two alternating tissues, generator, discriminator, betaVAE), all seeded"""
-    from rna_gan_amd import synth
-    from rna_gan_amd.resident import DeviceTileSet
-    size, features = int(config["img_size"]), int(config.get("rna_features", 19198))
-    patients, enc = int(config.get("synthetic_patients", 8)), int(config.get("encoding_dims", 64))
-    step = int(config.get("step_channels", 4))
-    n = patients * args.sample_size
-    row_of = torch.arange(n, dtype=torch.int32) % patients
-    ts = DeviceTileSet.from_tensors(synth.synthetic_tiles_u8(n, size, args.seed),
-                                    rna=synth.synthetic_rna(patients, features, args.seed + 1, distinct=patients), row_of=row_of,
-                                    labels=(row_of % 2).float(), device=device)
-    G = synth.seeded_fill_(P.DCGANGenerator(enc, size, 3, step, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.Tanh()),
-                           args.seed + 2).to(device)
-    D = synth.seeded_fill_(P.DCGANDiscriminator(size, 3, step, nonlinearity=nn.LeakyReLU(0.2), last_nonlinearity=nn.LeakyReLU(0.2)),
-                           args.seed + 3).to(device)
-    bv = synth.seeded_fill_(P.betaVAE(features, enc, [40, 36, enc], [36, 40], beta=0.0005), args.seed + 4).to(device)
-    return ts, G, D, bv
-
-
 def _file_inputs(args, config, device):
-    import random
-    from rna_gan_amd import data as PD
-    from rna_gan_amd.gan_utils import load_torchgan_trainer
-    from rna_gan_amd.resident import DeviceTileSet
+    from rna_gan_amd.gan_utils import load_torchgan_trainer, resident_training_set
     from rna_gan_amd.rna_tables import model_from_config
-    random.seed(args.seed)                                  # the per-slide key sample is drawn from the global ``random`` generator
-    table = PD.load_slide_tables(config["path_csv"], config["patch_data_path"])
-    table, _, _ = PD.log_standardize_rna(table)
-    ds = PD.PatchRNADataset(config["patch_data_path"], table, config["img_size"], max_patches_total=args.sample_size, transforms=None)
-    ts = DeviceTileSet.from_dataset(ds, device)             # unreadable records are dropped here, once
+    ts = resident_training_set(config, args.seed, args.sample_size, device)
     print("Real tiles on {}: {} tiles of {} expression rows, {} unreadable records skipped".format(device, len(ts), ts.rna.shape[0],
                                                                                                  ts.dropped))
     features = int(config.get("rna_features", ts.rna.shape[1]))
@@ -114,19 +84,19 @@ def _report(pred, y, C):
 
 def run(args):
     """the three settings as a dictionary; writes <out_dir>/probe.json"""
-    from rna_gan_amd import fid as FID
     from rna_gan_amd import linprobe as LP
-    from rna_gan_amd.metrics import _eval_mode
+    from rna_gan_amd import synth
+    from rna_gan_amd.metrics import _eval_mode, feature_extractor
     from rna_gan_amd.representation import tile_features
     with open(args.config) as f:
         config = json.load(f)
     print(10 * "-"); print("Config for this experiment \n"); print(config); print(10 * "-")
     device = torch.device("cuda:0")
-    ts, G, D, bv = (_synthetic_inputs if args.synthetic else _file_inputs)(args, config, device)
-    if args.extractor == "discriminator":
-        extract, resize = FID.discriminator_features_device(D), None
+    if args.synthetic:
+        ts, G, D, bv, _ = synth.evaluation_inputs(config, args.sample_size, args.seed, device, tissues=True)
     else:
-        extract, resize = FID.inception_features_device(args.extractor, device), 299
+        ts, G, D, bv = _file_inputs(args, config, device)
+    extract, resize = feature_extractor(args.extractor, D, device)
     try:      # one tissue per expression row, at least two tissues, enough tiles of each for the folds
         classes, y_real, row_label = LP.row_tissues(ts.labels.round().long(), ts.row_of, ts.rna.shape[0], args.folds)
     except ValueError as e:
